@@ -20,14 +20,19 @@ pair IDs (shard.DirtyGather: one all-gather into preallocated buffers; the
 gathered counts are read back after it and a capacity overflow is regrown and
 re-gathered inside the step).
 
-Beside the timed line (rank 0, N = 1): the roofline on both byte definitions
+A plain run (no --full) does what the headline needs and no more: ingest, warm
+up, time --steps steps, write the last step's results with --dump-outputs DIR,
+print the line (metric, value, unit, ms_per_step, the workload).  Everything
+below is measured or checked only with --full.
+
+Beside the timed line (--full; rank 0, N = 1): the roofline on both byte definitions
 (this build's format bytes, and SURVEY.md §8(d)'s B_pair = sum(24 L + V + 8) +
 O), end-to-end JSON-in rates (host-encoded and device-encoded, K0), the CPU
 baselines on all host cores (the C++ tree-walk restatement of the predicates
 and the CPU merge over the CSR encoding) and a three-way parity check of
 decisions and changed paths (GPU, tree-walk, CSR merge) on the CPU sample.
 
-Launch: python bench.py [--gpus N --steps K --warmup W].  For N > 1 either
+Launch: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR].  For N > 1 either
 under torch.distributed.run (one process per GPU; WORLD_SIZE must equal N) or
 bare, in which case bench.py starts that launch itself as a child process and
 relays rank 0's line.  Rank 0 prints one JSON line.
@@ -138,6 +143,16 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="config1..4: besides the timed line, everything else this bench measures and checks -- the "
+                         "full-size decision / changed-path checks against the generator and the CPU merge, the "
+                         "roofline and per-kernel times (isolated passes of their own), end-to-end JSON-in rates, the "
+                         "oracle sample, the CPU baselines and the three-way parity (each still subject to its own "
+                         "--no-* / size option).  Off: ingest, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="config1..4: after the timed steps rank 0 writes the results of the LAST timed step (what "
+                         "gpudiff_wait returns for it) as DIR/<name>.npy, float32 / float64, at most 64 MB in all: "
+                         "fixed seeded samples of the long arrays, their full sizes and checksums beside them")
     ap.add_argument("--config", default="config3", choices=["config1", "config2", "config3", "config4", "config5", "upsert", "rollup", "negotiate"],
                     help="config5 = watch replay through the device-resident object store (bench_replay.py); "
                          "upsert = the write path's request bodies, kernel K10 (bench_upsert.py); "
@@ -226,6 +241,8 @@ def main():
     args = ap.parse_args(argv)
     if not args.pipeline:
         args.pipeline = 2
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     self_launch(args, argv)
     claim_stdout()
     if args.gpus > 1 and args.config not in ("config1", "config2", "config3", "config4"):
@@ -294,8 +311,8 @@ def main():
     # full-size changed-path parity (north_star: bit-exact changed-path lists for all 10M pairs): the CPU
     # merge over the same CSR encoding (oracle/csr_ref.cpp, pinned to the oracle by tests/test_oracle_cpp.py)
     # decides and lists the paths of every chunk on the host while it is staged; checked against the
-    # GPU's first pass below.  Untimed.
-    cpu_parts = [] if not args.no_full_paths else None
+    # GPU's first pass below.  Untimed; --full only.
+    cpu_parts = [] if args.full and not args.no_full_paths else None
     t_cpu_paths = 0.0
 
     def cpu_paths(hb):
@@ -340,39 +357,12 @@ def main():
     # ---------------- warmup + full-size correctness (size-independent properties)
     ticket = eng.diff(db)
     res = eng.wait(ticket)
-    exp_flags = pop.expected_flags(truth)
-    got = res.pair_flags & (G.SPEC_DIRTY | G.STATUS_DIRTY)
-    n_bad = int((got != exp_flags).sum())
-    offs = res.path_offsets.astype(np.int64)
-    every_dirty_has_path = bool((np.diff(offs) >= 1).all()) if res.dirty_ids.size else True
-    ids_ok = (res.spec_dirty_ids.size == int((got & G.SPEC_DIRTY).astype(bool).sum()) and
-              res.status_dirty_ids.size == int((got & G.STATUS_DIRTY).astype(bool).sum()))
     n_spec, n_status, n_paths = int(res.spec_dirty_ids.size), int(res.status_dirty_ids.size), int(res.path_hashes.size)
-    full_check = dict(pairs=n, flag_mismatches=n_bad, every_dirty_pair_has_paths=every_dirty_has_path,
-                      id_lists_consistent=ids_ok, spec_dirty=n_spec, status_dirty=n_status, paths=n_paths)
-    if cpu_parts is not None:
-        c_flags = np.concatenate([q[0] for q in cpu_parts])
-        c_offs, base = [np.zeros(1, np.int64)], 0
-        for q in cpu_parts:
-            c_offs.append(q[1][1:].astype(np.int64) + base)
-            base += int(q[1][-1])
-        c_offs = np.concatenate(c_offs)
-        c_h = np.concatenate([q[2] for q in cpu_parts])
-        c_k = np.concatenate([q[3] for q in cpu_parts])
-        full_check.update(
-            flags_eq_cpu_csr=bool(np.array_equal(res.pair_flags & 7, c_flags)),
-            paths_eq_cpu_csr=bool(np.array_equal(offs, c_offs) and np.array_equal(res.path_hashes, c_h) and
-                                  np.array_equal(res.path_kinds, c_k)),
-            cpu_csr_paths=int(c_h.size), cpu_csr_seconds=round(t_cpu_paths, 2),
-            cpu_csr="oracle/csr_ref.cpp over every chunk's host CSR (decisions + changed-path lists, all pairs)")
-        if not (full_check["flags_eq_cpu_csr"] and full_check["paths_eq_cpu_csr"]):
-            log("FULL-SIZE PATH PARITY FAILED")
-        del cpu_parts, c_flags, c_offs, c_h, c_k
-    log("full-size check:", json.dumps(full_check))
-    if n_bad or not every_dirty_has_path or not ids_ok or full_check.get("paths_eq_cpu_csr") is False:
-        log("FULL-SIZE CHECK FAILED")
-    pop_flags = res.pair_flags.copy()
-    del res
+    full_check = pop_flags = None
+    if args.full:
+        full_check = full_size_check(G, pop, truth, res, cpu_parts, t_cpu_paths)
+        pop_flags = res.pair_flags.copy()
+    del res, cpu_parts
 
     for _ in range(max(0, args.warmup - 1)):
         eng.diff(db)
@@ -388,7 +378,8 @@ def main():
         dbs.append(db2)
         streams.append(stream2)
         r2 = eng2.wait(eng2.diff(db2))  # allocates its outputs; the same decisions as the first context's
-        full_check["pipeline_view_flags_eq"] = bool(np.array_equal(r2.pair_flags, pop_flags))
+        if full_check is not None:
+            full_check["pipeline_view_flags_eq"] = bool(np.array_equal(r2.pair_flags, pop_flags))
         del r2
         for _ in range(max(0, args.warmup - 1)):
             eng2.diff(db2)
@@ -466,13 +457,13 @@ def main():
     t0 = time.perf_counter()
     if args.pipeline == 2:  # alternate contexts: two passes in flight
         for i in range(args.steps):
-            engs[i & 1].diff(dbs[i & 1])
+            last_ticket = engs[i & 1].diff(dbs[i & 1])
             if gather is not None:
                 gather.step(fill_counts, fill_ids)
     for _ in range(args.steps if args.pipeline == 1 else 0):
         if gather is not None and (gather.bind is not None or gather.slot is not None):
             gather.begin_step()
-        eng.diff(db)
+        last_ticket = eng.diff(db)
         if gather is not None:
             gather.step(fill_counts, fill_ids)
     if gather is not None:
@@ -481,7 +472,11 @@ def main():
     if world > 1:
         dist.barrier()
     dt = time.perf_counter() - t0
-    if args.pipeline == 2:
+    if args.dump_outputs and rank == 0:
+        # the last timed step's pass is still its batch's current ticket (the isolated passes below replace it)
+        last = (args.steps - 1) & 1 if args.pipeline == 2 else 0
+        dump_outputs(args.dump_outputs, engs[last].wait(last_ticket))
+    if args.pipeline == 2 and args.full:
         # the timed loop overlaps passes, so a kernel's event span there includes waiting for CUs the other
         # pass holds: the roofline's kernel times come from isolated passes of the same batch (untimed)
         eng.timing_reset()
@@ -496,7 +491,7 @@ def main():
                 dist.barrier()
     tm = eng.timings()
     per_rank_ms = None
-    if collective:  # every rank's kernel times of its isolated passes (the rehearsal's per-rank K3, item 5)
+    if collective and args.full:  # every rank's kernel times of its isolated passes (the rehearsal's per-rank K3)
         t = torch.tensor([tm.compare_ms, tm.compact_ms, tm.join_ms, tm.emit_ms, tm.total_ms], dtype=torch.float64,
                          device=comm_dev)
         allt = [torch.zeros_like(t) for _ in range(world)]
@@ -522,7 +517,8 @@ def main():
         dist.all_reduce(tot)
         total_pairs = int(tot.item())
         if sa is not None:
-            gather_check.update(node_sets_vs_truth(pop, truth, sa, ta, dist, comm_dev, G))
+            if args.full:
+                gather_check.update(node_sets_vs_truth(pop, truth, sa, ta, dist, comm_dev, G))
             if args.dump_gather and rank == 0:
                 np.savez(args.dump_gather, spec=sa.cpu().numpy(), status=ta.cpu().numpy())
     else:
@@ -542,7 +538,7 @@ def main():
     achieved_pass = fmt_bytes / (pass_ms * 1e-3) / 1e9 if pass_ms > 0 else 0.0
     traffic, traffic_src = None, None
     src_hash = k2_source_hash()
-    tj = args.traffic_json
+    tj = args.traffic_json if args.full else "none"
     if tj == "latest":
         import glob
         found = sorted(glob.glob(os.path.join(ROOT, "profiles", "**", "*pmc_summary.json"), recursive=True),
@@ -573,7 +569,7 @@ def main():
 
     # ---------------- rank 0, N = 1: end-to-end JSON-in, CPU baselines, three-way parity
     json_in = cpu = sample_check = three_way = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         if args.json_in_pairs:
             json_in = json_in_rates(G, pop, min(args.json_in_pairs, n), threads, local_rank)
             log("json-in:", json.dumps(json_in))
@@ -673,10 +669,87 @@ def main():
             # the loaded library's content hash of its sources (gpudiff_build_id; the loader refused it unless
             # it equals the shipped sources' hash, kcp_amd/buildinfo.py)
             "build_id": G.BUILD_ID, "build_verified": G.BUILD_VERIFIED,
+            "full": args.full,
         }
+        if not args.full:
+            # a plain run ran no isolated passes: the engine's kernel times are the overlapped timed loop's,
+            # which is no roofline
+            line.update(roofline=None, kernels_ms=None)
         print(json.dumps(line), flush=True)
     if collective:
         dist.destroy_process_group()
+
+
+def full_size_check(G, pop, truth, res, cpu_parts, t_cpu_paths):
+    """--full: the first pass's results over the whole population against the generator's ground truth (size-
+    independent properties) and, with cpu_parts (the CPU merge's decisions and changed-path lists of every
+    ingested chunk), bit for bit against those."""
+    n = pop.n
+    exp_flags = pop.expected_flags(truth)
+    got = res.pair_flags & (G.SPEC_DIRTY | G.STATUS_DIRTY)
+    n_bad = int((got != exp_flags).sum())
+    offs = res.path_offsets.astype(np.int64)
+    every_dirty_has_path = bool((np.diff(offs) >= 1).all()) if res.dirty_ids.size else True
+    ids_ok = (res.spec_dirty_ids.size == int((got & G.SPEC_DIRTY).astype(bool).sum()) and
+              res.status_dirty_ids.size == int((got & G.STATUS_DIRTY).astype(bool).sum()))
+    n_spec, n_status, n_paths = int(res.spec_dirty_ids.size), int(res.status_dirty_ids.size), int(res.path_hashes.size)
+    full_check = dict(pairs=n, flag_mismatches=n_bad, every_dirty_pair_has_paths=every_dirty_has_path,
+                      id_lists_consistent=ids_ok, spec_dirty=n_spec, status_dirty=n_status, paths=n_paths)
+    if cpu_parts is not None:
+        c_flags = np.concatenate([q[0] for q in cpu_parts])
+        c_offs, base = [np.zeros(1, np.int64)], 0
+        for q in cpu_parts:
+            c_offs.append(q[1][1:].astype(np.int64) + base)
+            base += int(q[1][-1])
+        c_offs = np.concatenate(c_offs)
+        c_h = np.concatenate([q[2] for q in cpu_parts])
+        c_k = np.concatenate([q[3] for q in cpu_parts])
+        full_check.update(
+            flags_eq_cpu_csr=bool(np.array_equal(res.pair_flags & 7, c_flags)),
+            paths_eq_cpu_csr=bool(np.array_equal(offs, c_offs) and np.array_equal(res.path_hashes, c_h) and
+                                  np.array_equal(res.path_kinds, c_k)),
+            cpu_csr_paths=int(c_h.size), cpu_csr_seconds=round(t_cpu_paths, 2),
+            cpu_csr="oracle/csr_ref.cpp over every chunk's host CSR (decisions + changed-path lists, all pairs)")
+        if not (full_check["flags_eq_cpu_csr"] and full_check["paths_eq_cpu_csr"]):
+            log("FULL-SIZE PATH PARITY FAILED")
+    log("full-size check:", json.dumps(full_check))
+    if n_bad or not every_dirty_has_path or not ids_ok or full_check.get("paths_eq_cpu_csr") is False:
+        log("FULL-SIZE CHECK FAILED")
+    return full_check
+
+
+# --dump-outputs: elements kept of one array (float32: 16 MiB, float64: 4 MiB; 2 + 6 arrays stay under 64 MB)
+DUMP_CAP = {np.float32: 1 << 22, np.float64: 1 << 19}
+DUMP_SEED = 20211004
+
+
+def dump_outputs(out_dir, res):
+    """Writes one diff pass's results (a gpudiff.DiffResult: what gpudiff_wait hands the caller) as
+    out_dir/<name>.npy.  u8 arrays go out as float32 and u32 ones as float64 (both exact); the 64-bit path
+    hashes as their low and high 32 bits.  An array longer than its cap is cut to a fixed, seeded sample of
+    its elements (the same indices whenever the length is the same, in index order); sizes.npy holds every
+    array's full length and checksums.npy the sum mod 2^64 of every full array, as (low, high) 32-bit halves,
+    in the order of DiffResult's fields -- so two builds can be compared on all of it."""
+    os.makedirs(out_dir, exist_ok=True)
+    fields = [("pair_flags", np.float32), ("spec_dirty_ids", np.float64), ("status_dirty_ids", np.float64),
+              ("dirty_ids", np.float64), ("path_offsets", np.float64), ("path_hashes", np.float64),
+              ("path_kinds", np.float32)]
+    sizes, sums = [], []
+    for name, ft in fields:
+        a = getattr(res, name)
+        sizes.append(a.size)
+        s = int(a.sum(dtype=np.uint64))
+        sums += [s & 0xFFFFFFFF, s >> 32]
+        if a.size > DUMP_CAP[ft]:
+            a = a[np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, DUMP_CAP[ft], replace=False))]
+        if name == "path_hashes":
+            np.save(os.path.join(out_dir, "path_hashes_lo.npy"), (a & np.uint64(0xFFFFFFFF)).astype(ft))
+            np.save(os.path.join(out_dir, "path_hashes_hi.npy"), (a >> np.uint64(32)).astype(ft))
+        else:
+            np.save(os.path.join(out_dir, name + ".npy"), a.astype(ft))
+    np.save(os.path.join(out_dir, "sizes.npy"), np.array(sizes, dtype=np.float64))
+    np.save(os.path.join(out_dir, "checksums.npy"), np.array(sums, dtype=np.float64))
+    log("dumped the last timed step's results to %s: %s" % (out_dir, dict(zip([f for f, _ in fields], sizes))))
 
 
 def box_id():

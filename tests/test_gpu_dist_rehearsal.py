@@ -28,7 +28,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_two_ranks_gloo_on_one_gpu(tmp_path, pipeline, cap_frac):
     dump = str(tmp_path / "gather.npz")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--pairs", "100000", "--clusters", "1000",
-           "--dist-backend", "gloo", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--sample", "0",
+           "--dist-backend", "gloo", "--steps", "4", "--warmup", "1", "--full", "--no-cpu-baseline", "--sample", "0",
            "--json-in-pairs", "0", "--threads", "8", "--dump-gather", dump, "--pipeline", str(pipeline),
            "--gather-cap-frac", str(cap_frac), "--calib-passes", "1"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=240,

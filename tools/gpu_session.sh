@@ -14,7 +14,7 @@ timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke(); print('smok
 tail -1 $O/smoke.log
 fi
 if [ -z "$SKIP_C3" ]; then
-timeout -k 10 400 python bench.py > $O/bench_config3.json 2> $O/bench_config3.log || { tail -30 $O/bench_config3.log; exit 1; }
+timeout -k 10 400 python bench.py --full > $O/bench_config3.json 2> $O/bench_config3.log || { tail -30 $O/bench_config3.log; exit 1; }
 cat $O/bench_config3.json
 fi
 if [ -z "$SKIP_C5" ]; then
