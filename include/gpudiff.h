@@ -106,7 +106,12 @@ enum {
                                             pairs through the deferred K4 path) */
 #define GPUDIFF_OPT_DEVICE_ENCODE 0x2000000u /* gpudiff_submit / single-pair helpers: raw JSON up, kernel K0
                                                 encodes (as GPUDIFF_STORE_DEVICE_ENCODE does for the store) */
-#define GPUDIFF_OPT_KNOWN (GPUDIFF_OPT_TIMING | (0xFu << GPUDIFF_OPT_ARENA_SHIFT) | GPUDIFF_OPT_DEVICE_ENCODE)
+#define GPUDIFF_OPT_PATH_STRINGS 0x8000000u  /* device-encoded batches (gpudiff_submit with GPUDIFF_OPT_DEVICE_ENCODE,
+                                                gpudiff_store_submit on a GPUDIFF_STORE_DEVICE_ENCODE store): kernels
+                                                K15 / K16 render every changed path as text inside gpudiff_wait
+                                                (gpudiff_result_path_strings) */
+#define GPUDIFF_OPT_KNOWN \
+    (GPUDIFF_OPT_TIMING | (0xFu << GPUDIFF_OPT_ARENA_SHIFT) | GPUDIFF_OPT_DEVICE_ENCODE | GPUDIFF_OPT_PATH_STRINGS)
 
 #define GPUDIFF_DEVICE_CURRENT (-1)
 #define GPUDIFF_DEVICE_NONE (-2)   /* host-only context: encoding only */
@@ -158,6 +163,37 @@ typedef struct gpudiff_result {
     const uint8_t* path_kinds;
     void* internal_;
 } gpudiff_result;
+
+/* ---- changed paths as text (GPUDIFF_OPT_PATH_STRINGS) ----
+ * The batch's changed paths rendered from the path tables its blobs carry in HBM (gpudiff_format.h): string i
+ * belongs to path_hashes[i] / path_kinds[i].  A key is its raw decoded bytes (any byte, NUL included), preceded by
+ * '.' only when the text before it is non-empty; an index is "[%u]"; the GPUDIFF_PATH_STATUS_ABSENT sentinel is
+ * "status" -- the text gpudiff_resolve_path gives, without decoding a document again.  Pairs the host resolved
+ * (K0's deferrals) get their strings from the host encoder's flattened objects: n_host counts those entries.
+ * n_unresolved counts entries whose table walk failed (rendered empty): always 0 for tables the engine wrote.
+ * The arrays belong to the result (valid until gpudiff_result_release).
+ * GPUDIFF_E_STATE: the option was off, the batch was encoded on the host (gpudiff_submit without
+ * GPUDIFF_OPT_DEVICE_ENCODE or after its GPUDIFF_E_CAPACITY fallback: gpudiff_resolve_path serves those), or the
+ * store is not a GPUDIFF_STORE_DEVICE_ENCODE one. */
+typedef struct gpudiff_path_strings {
+    size_t n_paths;            /* == result.n_paths, same order as path_hashes / path_kinds */
+    const uint64_t* offsets;   /* n_paths + 1 */
+    const char* bytes;         /* string i = bytes[offsets[i], offsets[i+1]) -- raw key bytes, no terminator */
+    size_t n_host;             /* entries rendered by the host path */
+    size_t n_unresolved;       /* must be 0; such entries are empty */
+} gpudiff_path_strings;
+int gpudiff_result_path_strings(gpudiff_ctx* ctx, const gpudiff_result* res, gpudiff_path_strings* out);
+/* what the context has rendered so far; kernel_ms needs GPUDIFF_OPT_TIMING (HIP events around K15 + scan and
+ * around the offsets + K16, summed over timed_batches) */
+typedef struct gpudiff_path_stats {
+    uint64_t batches;        /* waited batches with the option on */
+    uint64_t paths;          /* strings, the host-rendered ones included */
+    uint64_t bytes;
+    uint64_t host_paths;
+    double kernel_ms;
+    uint64_t timed_batches;
+} gpudiff_path_stats;
+int gpudiff_path_strings_stats_get(gpudiff_ctx* ctx, gpudiff_path_stats* out);
 
 /* device-side view of a diffed batch (for RCCL gathers; pointers are HBM).  The pointers belong to the batch's
  * current result slot: after gpudiff_dbatch_result_slot switches slots, fetch the view again (counts included --
@@ -416,6 +452,15 @@ int gpudiff_encode_objects(gpudiff_ctx* ctx, const uint8_t* const* docs, const s
                            size_t n, uint8_t* out, uint64_t out_cap, gpudiff_obj_info* info);
 int gpudiff_encode_object_host(const uint8_t* doc, size_t len, uint32_t seed, uint32_t path_hash_bits, uint8_t* out,
                                uint64_t out_cap, gpudiff_obj_info* info);
+/* Renders the path of `path_hash` (masked, as reported in gpudiff_result.path_hashes) from one object's blob in
+ * the device-store format: `blob` points at the blob itself (out + info->off of gpudiff_encode_objects, out of
+ * gpudiff_encode_object_host), `seed` is the seed it was encoded under.  No GPU needed: the walk kernels K15 / K16
+ * do, on the host.  Writes *out_len bytes into buf, raw key bytes, no terminator.
+ * GPUDIFF_E_NOTFOUND: the hash is not in the table (or its chain of parents does not reach the root within 256
+ * nodes); GPUDIFF_E_STATE: the blob has no valid table (n_tab == GPUDIFF_TAB_NONE) or was not encoded;
+ * GPUDIFF_E_CAPACITY: the text is longer than cap, *out_len is still set. */
+int gpudiff_render_path_from_blob(const uint8_t* blob, const gpudiff_obj_info* info, uint32_t seed,
+                                  uint64_t path_hash, char* buf, size_t cap, size_t* out_len);
 /* profiling hook: K0 per-phase wall-clock ticks (100 MHz, summed over waves) since the
  * previous call (scan, tree, values, hashes, sort, blob, -, -); enable != 0
  * keeps recording */

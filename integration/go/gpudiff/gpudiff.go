@@ -298,6 +298,53 @@ type Batcher struct {
 	// oldest, so a pipelined batcher must be the engine's only gpudiff_submit user (no one-pair helpers on it).
 	pipelined bool
 	bufs      []*jsonBuf // idle flush buffers (getJSONBuf)
+	// onPaths (WithPaths): called for every dirty event, before its enqueue, with the event's changed field
+	// paths as the engine rendered them (OptPathStrings on a device-encode engine / store)
+	onPaths func(obj interface{}, paths []ChangedPath)
+}
+
+// ChangedPath is one entry of a dirty pair's changed-path list with its text ("spec.replicas", raw key bytes).
+type ChangedPath struct {
+	Hash uint64
+	Kind uint8 // GPUDIFF_PATH_* | GPUDIFF_PATH_REGION_STATUS
+	Path string
+}
+
+// OptPathStrings (with OptDeviceEncode, or a device-encode Store): kernels K15 / K16 render every changed path as
+// text inside gpudiff_wait; the batcher hands them to WithPaths' callback.
+const OptPathStrings = uint32(C.GPUDIFF_OPT_PATH_STRINGS)
+
+// WithPaths sets the callback that receives each dirty event's changed paths (PathStrings below); without
+// OptPathStrings, or for a batch the engine encoded on the host, it is never called.
+func (b *Batcher) WithPaths(fn func(obj interface{}, paths []ChangedPath)) *Batcher {
+	b.onPaths = fn
+	return b
+}
+
+// PathStrings copies a waited result's changed paths out, per dirty pair in result order (nil when the engine
+// rendered none: gpudiff_result_path_strings returns GPUDIFF_E_STATE).  Call before gpudiff_result_release.
+func (e *Engine) PathStrings(res *C.gpudiff_result) [][]ChangedPath {
+	var ps C.gpudiff_path_strings
+	if C.gpudiff_result_path_strings(e.ctx, res, &ps) != C.GPUDIFF_OK {
+		return nil
+	}
+	nd, np := int(res.n_dirty), int(ps.n_paths)
+	out := make([][]ChangedPath, nd)
+	if np == 0 {
+		return out
+	}
+	poff := (*[1 << 28]C.uint32_t)(unsafe.Pointer(res.path_offsets))[: nd+1 : nd+1]
+	hs := (*[1 << 28]C.uint64_t)(unsafe.Pointer(res.path_hashes))[:np:np]
+	ks := (*[1 << 30]C.uint8_t)(unsafe.Pointer(res.path_kinds))[:np:np]
+	offs := (*[1 << 28]C.uint64_t)(unsafe.Pointer(ps.offsets))[: np+1 : np+1]
+	for k := 0; k < nd; k++ {
+		for q := int(poff[k]); q < int(poff[k+1]); q++ {
+			txt := C.GoStringN((*C.char)(unsafe.Pointer(uintptr(unsafe.Pointer(ps.bytes))+uintptr(offs[q]))),
+				C.int(offs[q+1]-offs[q]))
+			out[k] = append(out[k], ChangedPath{Hash: uint64(hs[q]), Kind: uint8(ks[q]), Path: txt})
+		}
+	}
+	return out
 }
 
 func (b *Batcher) bytesHint(n int) int { return int(b.avgBytes*float64(n)*1.25) + 4096 }
@@ -610,6 +657,7 @@ func (b *Batcher) submitFlight(evs []event) *flight {
 // like the reference's failed type assertion -> enqueue, specsyncer.go:20-22).
 func (b *Batcher) finishFlight(f *flight) {
 	flags := make([]uint8, f.n)
+	var paths map[int][]ChangedPath // OptPathStrings + WithPaths: pair index -> its changed paths
 	rc := f.rc
 	if f.n > 0 {
 		b.e.mu.Lock()
@@ -619,6 +667,15 @@ func (b *Batcher) finishFlight(f *flight) {
 		}
 		if rc == C.GPUDIFF_OK {
 			copy(flags, (*[1 << 30]uint8)(unsafe.Pointer(res.pair_flags))[:f.n:f.n])
+			if b.onPaths != nil {
+				if ps := b.e.PathStrings(&res); ps != nil { // per dirty pair; dirty_ids are the pairs' indices
+					ids := (*[1 << 28]C.uint32_t)(unsafe.Pointer(res.dirty_ids))[:len(ps):len(ps)]
+					paths = make(map[int][]ChangedPath, len(ps))
+					for k := range ps {
+						paths[int(ids[k])] = ps[k]
+					}
+				}
+			}
 			C.gpudiff_result_release(b.e.ctx, &res)
 		}
 		b.e.mu.Unlock()
@@ -626,6 +683,9 @@ func (b *Batcher) finishFlight(f *flight) {
 	for i, ev := range f.evs {
 		k := f.pairOf[i]
 		if k < 0 || rc != C.GPUDIFF_OK || !f.ok[k] || flags[k]&uint8(ev.which) != 0 {
+			if p, have := paths[k]; have && f.ok[k] {
+				b.onPaths(ev.new, p)
+			}
 			ev.enqueue(ev.new)
 		}
 	}

@@ -870,6 +870,28 @@ int collect_results(gpudiff_ctx* c, gpudiff_dbatch* d, ResultStore& rsr) {
 
 extern "C" {
 
+int gpudiff_result_path_strings(gpudiff_ctx* c, const gpudiff_result* res, gpudiff_path_strings* out) {
+    (void)c;
+    if (!res || !out) return GPUDIFF_E_INVAL;
+    memset(out, 0, sizeof(*out));
+    const ResultStore* rs = (const ResultStore*)res->internal_;
+    // rendered by the device-encode finisher only (dstore.cpp): a host-encoded batch has no path tables
+    if (!rs || !rs->ps.on) return GPUDIFF_E_STATE;
+    out->n_paths = rs->ps.n;
+    out->offsets = rs->ps.offsets();
+    out->bytes = rs->ps.bytes();
+    out->n_host = rs->ps.n_host;
+    out->n_unresolved = rs->ps.n_unresolved;
+    return GPUDIFF_OK;
+}
+
+int gpudiff_path_strings_stats_get(gpudiff_ctx* c, gpudiff_path_stats* out) {
+    if (!c || !out) return GPUDIFF_E_INVAL;
+    if (!(c->flags & GPUDIFF_OPT_PATH_STRINGS)) return GPUDIFF_E_STATE;
+    *out = c->path_stats;
+    return GPUDIFF_OK;
+}
+
 void gpudiff_result_release(gpudiff_ctx* c, gpudiff_result* res) {
     (void)c;
     if (!res) return;

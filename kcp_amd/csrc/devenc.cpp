@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "engine.h"
+#include "pathstr.h"
 #include "tokenize.h"
 
 using namespace gd;
@@ -53,6 +54,22 @@ int gpudiff_encode_object_host(const uint8_t* doc, size_t len, uint32_t seed, ui
         memcpy(out, pool.data() + off, bytes);
     }
     return GPUDIFF_OK;
+}
+
+int gpudiff_render_path_from_blob(const uint8_t* blob, const gpudiff_obj_info* info, uint32_t seed,
+                                  uint64_t path_hash, char* buf, size_t cap, size_t* out_len) {
+    if (!blob || !info || seed > 255 || (cap && !buf)) return GPUDIFF_E_INVAL;
+    if (out_len) *out_len = 0;
+    if (info->status != GPUDIFF_TOK_OK || info->n_tab == GPUDIFF_TAB_NONE) return GPUDIFF_E_STATE;
+    const uint64_t body = gpudiff_blob_body(info->spec_l, info->spec_ar, info->stat_l, info->stat_ar);
+    if (body > info->bytes || 24ull * info->n_tab > info->bytes - body) return GPUDIFF_E_INVAL;
+    const PathTab t = path_tab(blob + body, info->n_tab, info->bytes - body);
+    // the root's hash is the seed under any mask (seeds are <= 255, hashes keep >= 8 bits)
+    const uint64_t len = path_text_len(t, seed, path_hash);
+    if (len == kPathUnresolved) return GPUDIFF_E_NOTFOUND;
+    if (out_len) *out_len = (size_t)len;
+    if (len > cap) return GPUDIFF_E_CAPACITY;
+    return path_text_write(t, seed, path_hash, (uint8_t*)buf, len) ? GPUDIFF_OK : GPUDIFF_E_NOTFOUND;
 }
 
 int gpudiff_encode_objects(gpudiff_ctx* c, const uint8_t* const* docs, const size_t* lens, const uint32_t* seeds,

@@ -24,6 +24,7 @@
 // ticket returns (deferred events are re-read), and batches are waited in
 // submit order, at most two in flight.
 #include "dstore.h"
+#include "pathstr.h"
 
 #include <emmintrin.h>
 #include <string.h>
@@ -88,6 +89,17 @@ struct Ring {
     uint64_t bound = 0;
     gpudiff_ticket ticket = 0;
     bool outstanding = false;
+    // GPUDIFF_OPT_PATH_STRINGS (render_paths): cached here and grown on demand, never allocated per batch
+    bool strs = false;            // this batch was submitted with the option on
+    uint32_t space_idx = 0;       // the space its blobs were written to
+    uint32_t* dntab = nullptr;    // K0x: per row, the path-table entry counts of its old and new blob
+    uint64_t ntab_cap = 0;
+    uint64_t* ps_len = nullptr;   // K15: the strings' lengths
+    uint64_t* ps_tiles = nullptr;  // the scan's tile sums
+    unsigned long long* ps_ctr = nullptr;  // total bytes, unresolved entries
+    uint8_t* ps_out = nullptr;    // offsets[n + 1] | bytes: one D2H
+    uint64_t ps_len_cap = 0, ps_tiles_cap = 0, ps_out_cap = 0;
+    hipEvent_t ps_ev[4] = {};     // GPUDIFF_OPT_TIMING: K15 + scan begin/end, offsets + K16 begin/end
 };
 
 // gpudiff_host_alloc's pinned buffers: a gpudiff_submit batch laid out in one of them (gpudiff.h) is uploaded
@@ -235,6 +247,10 @@ int before_st_slot_op(DStore* s) {
 // exact append point back
 int compact(DStore* s) {
     gpudiff_ctx* c = s->c;
+    // GPUDIFF_OPT_PATH_STRINGS: a batch in flight renders its paths from the space it was written to; packing into
+    // that space would overwrite its superseded blobs first (dstore_submit refuses such a submit before it gets here)
+    for (const Ring& R : s->ring)
+        if (R.outstanding && R.strs && R.space_idx == 1 - s->cur) return GPUDIFF_E_STATE;
     if (int rc = before_st_slot_op(s)) return rc;
     HIPCHK(launch_compact_store(c->stream, s->slots, s->max_slots, s->space[s->cur], s->space[1 - s->cur], s->sizes,
                                 s->tile_sums, s->used_dev));
@@ -255,6 +271,128 @@ int ensure_space(DStore* s, uint64_t want, uint64_t need) {
     int rc = compact(s);
     if (rc) return rc;
     return s->used_ub + need <= s->space_bytes ? GPUDIFF_OK : GPUDIFF_E_CAPACITY;
+}
+
+// ------------------------------------------------------------------ changed paths as text
+// GPUDIFF_OPT_PATH_STRINGS: K15 + scan + K16 (paths.hip) over a waited batch's changed-path lists, on the readback
+// stream (never behind the next batch's work).  Runs in the finisher between collect_results (the counts; the diff
+// pass is done) and resolve(): until then the batch's rows, its changed-path lists and both sides' blobs are as the
+// diff pass read them, in the space the batch was written to (R.d->pool) -- DESIGN.md "Changed paths as text".
+int render_paths(DStore* s, Ring& R, ResultStore& rs) {
+    gpudiff_ctx* c = s->c;
+    gpudiff_dbatch* d = R.d;
+    PathStrs& ps = rs.ps;
+    ps.on = true;
+    ps.n = rs.hashes.size();
+    ps.words.assign(1, 0);
+    c->path_stats.batches++;
+    if (!ps.n) return GPUDIFF_OK;
+    if (ps.n > 0xFFFFFFFFull) return GPUDIFF_E_CAPACITY;
+    int rc;
+    const uint32_t n = (uint32_t)ps.n;
+    if ((rc = grow_dev(&R.ps_len, &R.ps_len_cap, n)) || (rc = grow_dev(&R.ps_tiles, &R.ps_tiles_cap, path_tiles(n) + 1)))
+        return rc;
+    if (!R.ps_ctr && (rc = dalloc(&R.ps_ctr, 2))) return rc;
+    const bool timing = (c->flags & GPUDIFF_OPT_TIMING) != 0;
+    if (timing && !R.ps_ev[0])
+        for (auto& e : R.ps_ev) HIPCHK(hipEventCreate(&e));
+    PathJob j{d->rows,     R.dntab,      d->dirty_idx,  d->path_off,           d->out_h, d->out_k,
+              d->pool,     d->pool_cap,  c->hash_mask,  (uint32_t)rs.dirty.size(), n};
+    hipStream_t st = c->rb;
+    unsigned long long ctr[2] = {0, 0};
+    if (timing) HIPCHK(hipEventRecord(R.ps_ev[0], st));
+    HIPCHK(launch_path_len(st, j, R.ps_len, R.ps_tiles, R.ps_ctr));
+    if (timing) HIPCHK(hipEventRecord(R.ps_ev[1], st));
+    HIPCHK(hipMemcpyAsync(ctr, R.ps_ctr, 8, hipMemcpyDeviceToHost, st));  // the bytes to make room for
+    HIPCHK(hipStreamSynchronize(st));
+    const uint64_t head = 8ull * ((uint64_t)n + 1), total = ctr[0];
+    if ((rc = grow_dev(&R.ps_out, &R.ps_out_cap, head + total + 8))) return rc;
+    if (timing) HIPCHK(hipEventRecord(R.ps_ev[2], st));
+    HIPCHK(launch_path_write(st, j, R.ps_len, R.ps_tiles, (uint64_t*)R.ps_out, R.ps_out + head, total, R.ps_ctr));
+    if (timing) HIPCHK(hipEventRecord(R.ps_ev[3], st));
+    try {
+        ps.words.assign((size_t)n + 1 + (size_t)((total + 7) / 8), 0);
+    } catch (const std::bad_alloc&) {
+        return GPUDIFF_E_NOMEM;
+    }
+    HIPCHK(hipMemcpyAsync(ps.words.data(), R.ps_out, head + total, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(ctr, R.ps_ctr, 16, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    ps.n_unresolved = (size_t)ctr[1];
+    if (ps.words[n] != total) return GPUDIFF_E_DEVICE;  // the offsets the strings were written by
+    if (timing) {
+        float a = 0, b = 0;
+        HIPCHK(hipEventElapsedTime(&a, R.ps_ev[0], R.ps_ev[1]));
+        HIPCHK(hipEventElapsedTime(&b, R.ps_ev[2], R.ps_ev[3]));
+        c->path_stats.kernel_ms += (double)a + b;
+        c->path_stats.timed_batches++;
+    }
+    return GPUDIFF_OK;
+}
+
+// The host resolution's side of it: what renders a deferred event's changed paths once its diff is known -- per
+// side, the flattened object's leaves (hash -> path bytes, as hashed under the pair's final seed) or, for a
+// resident old side, its path table.
+struct HostSide {
+    struct Leaf {
+        uint64_t h;
+        uint32_t off, len;
+    };
+    std::vector<Leaf> spec, stat;  // ascending by h
+    std::string paths;
+    PathTable tab;  // a resident blob's (load_tab), walked by pathstr.h
+    uint32_t seed = 0;
+    bool flat = false, table = false;
+    void of_flat(const FlatObject& o) {
+        flat = true;
+        table = false;
+        paths = o.paths;
+        spec.clear();
+        stat.clear();
+        for (const LeafRec& r : o.spec) spec.push_back(Leaf{r.h, r.path_off, r.path_len});
+        for (const LeafRec& r : o.stat) stat.push_back(Leaf{r.h, r.path_off, r.path_len});
+    }
+    void of_table(const PathTable& t, uint32_t sd) {
+        flat = false;
+        table = true;
+        tab = t;
+        seed = sd;
+    }
+    bool render(uint64_t h, bool status, uint64_t mask, std::string& out) const {
+        out.clear();
+        if (flat) {
+            const std::vector<Leaf>& v = status ? stat : spec;
+            auto it = std::lower_bound(v.begin(), v.end(), h, [](const Leaf& l, uint64_t x) { return l.h < x; });
+            if (it == v.end() || it->h != h) return false;
+            out = render_path(paths.data() + it->off, it->len);
+            return true;
+        }
+        if (!table || tab.n == GPUDIFF_TAB_NONE) return false;
+        const PathTab t = path_tab(tab.data.data(), tab.n, tab.data.size());
+        const uint64_t root = (uint64_t)seed & mask, len = path_text_len(t, root, h);
+        if (len == kPathUnresolved) return false;
+        out.resize(len);
+        return path_text_write(t, root, h, (uint8_t*)&out[0], len);
+    }
+};
+struct HostPaths {
+    HostSide a, b;
+};
+
+// entry q of `r`'s changed paths (a deferred event's, diffed from host-encoded blobs) as text
+void host_path(const HostPaths& hp, const ResultStore& r, uint32_t q, uint64_t mask, PathStrs& out) {
+    const uint8_t k = r.kinds[q];
+    std::string s;
+    bool ok = true;
+    if ((k & 3u) == GPUDIFF_PATH_STATUS_ABSENT) s = "status";
+    else ok = ((k & 3u) == GPUDIFF_PATH_REMOVED ? hp.a : hp.b).render(r.hashes[q], (k & GPUDIFF_PATH_REGION_STATUS) != 0,
+                                                                     mask, s);
+    if (!ok) {
+        s.clear();
+        out.n_unresolved++;
+    }
+    out.push(s.data(), s.size());
+    out.n_host++;
 }
 
 // ------------------------------------------------------------------ host resolution
@@ -326,6 +464,10 @@ int resolve(DStore* s, Ring& R, ResultStore& rs) {
     FlatObject fn, fo;
     std::vector<uint8_t> pool;
     std::vector<gpudiff_pair_row> rows(drows.size());
+    // GPUDIFF_OPT_PATH_STRINGS: these events' strings come from the objects flattened here (their blobs carry no
+    // table in pair mode, the re-encoded old side none in store mode)
+    const bool strs = rs.ps.on;
+    std::vector<HostPaths> hp(strs ? drows.size() : 0);
     std::unordered_map<uint32_t, HostSlot> hs;
     std::vector<uint32_t> touched;
     for (size_t k = 0; k < drows.size(); k++) {
@@ -345,6 +487,10 @@ int resolve(DStore* s, Ring& R, ResultStore& rs) {
                 r.off_b = kRelTag | ob;
                 r.flags_a = (fo.flags & GPUDIFF_OBJ_HAS_STATUS) | (seed << GPUDIFF_OBJ_SEED_SHIFT);
                 r.flags_b = (fn.flags & GPUDIFF_OBJ_HAS_STATUS) | (seed << GPUDIFF_OBJ_SEED_SHIFT);
+                if (strs) {
+                    hp[k].a.of_flat(fo);
+                    hp[k].b.of_flat(fn);
+                }
             } else {
                 r.flags_a = r.flags_b = GPUDIFF_OBJ_DECODE_ERR;
             }
@@ -379,6 +525,7 @@ int resolve(DStore* s, Ring& R, ResultStore& rs) {
             a_tl = S.tl;
             a_tar = S.tar;
             a_of = S.has_status ? GPUDIFF_OBJ_HAS_STATUS : 0u;
+            if (strs) hp[k].a.of_table(S.tab, S.seed);  // the table load_tab fetched (or the previous event's)
         };
         if (S.live && S.seed == 0) {
             if ((rc = load_tab(s, S))) return rc;
@@ -394,6 +541,7 @@ int resolve(DStore* s, Ring& R, ResultStore& rs) {
                 a_live = true;
                 a_off = kRelTag | off;
                 a_of = fo.flags & GPUDIFF_OBJ_HAS_STATUS;
+                if (strs) hp[k].a.of_flat(fo);
                 s->st.old_encoded++;
                 if (S.live) s->st.reseeded++;
                 ok = true;
@@ -428,6 +576,7 @@ int resolve(DStore* s, Ring& R, ResultStore& rs) {
         uint64_t off;
         uint32_t sl, sar, tl, tar, bytes;
         enc.write_object_tab(fn, pool, &off, &sl, &sar, &tl, &tar, &bytes);
+        if (strs && !pair_error) hp[k].b.of_flat(fn);
         if (!pair_error) {
             r.off_a = a_live ? a_off : 0;
             r.spec_l_a = a_sl;
@@ -500,6 +649,11 @@ int resolve(DStore* s, Ring& R, ResultStore& rs) {
         ResultStore out;
         out.flags.resize(R.nev);
         out.off.push_back(0);
+        if (strs) {
+            out.ps.on = true;
+            out.ps.n_unresolved = rs.ps.n_unresolved;
+            out.ps.begin();
+        }
         size_t jr = 0;
         for (uint32_t i = 0; i < R.nev; i++) {
             uint8_t f = rs.flags[i];
@@ -522,10 +676,12 @@ int resolve(DStore* s, Ring& R, ResultStore& rs) {
                 for (uint32_t q = lo; q < hi; q++) {
                     out.hashes.push_back(rs.hashes[q]);
                     out.kinds.push_back(rs.kinds[q]);
+                    if (strs) out.ps.push(rs.ps.bytes() + rs.ps.offsets()[q], rs.ps.offsets()[q + 1] - rs.ps.offsets()[q]);
                 }
                 out.off.push_back((uint32_t)out.hashes.size());
             }
         }
+        if (strs) out.ps.finish();
         rs = std::move(out);
         return GPUDIFF_OK;
     }
@@ -567,6 +723,11 @@ int resolve(DStore* s, Ring& R, ResultStore& rs) {
     ResultStore out;
     out.flags.resize(R.nev);
     out.off.push_back(0);
+    if (strs) {
+        out.ps.on = true;
+        out.ps.n_unresolved = rs.ps.n_unresolved;
+        out.ps.begin();
+    }
     size_t jr = 0, j2 = 0, k = 0;
     for (uint32_t i = 0; i < R.nev; i++) {
         const bool d_in = (rs.flags[i] & (GPUDIFF_SPEC_DIRTY | GPUDIFF_STATUS_DIRTY)) != 0;
@@ -578,6 +739,7 @@ int resolve(DStore* s, Ring& R, ResultStore& rs) {
             jr++;
         }
         uint8_t f = rs.flags[i];
+        const size_t kd = k;  // the deferred event's index (rows, hp)
         if (def[i]) {
             f = r2.flags[k++];
             src = &r2;
@@ -597,10 +759,14 @@ int resolve(DStore* s, Ring& R, ResultStore& rs) {
             for (uint32_t q = lo; q < hi; q++) {
                 out.hashes.push_back(src->hashes[q]);
                 out.kinds.push_back(src->kinds[q]);
+                if (!strs) continue;
+                if (src == &r2) host_path(hp[kd], r2, q, c->hash_mask, out.ps);
+                else out.ps.push(rs.ps.bytes() + rs.ps.offsets()[q], rs.ps.offsets()[q + 1] - rs.ps.offsets()[q]);
             }
             out.off.push_back((uint32_t)out.hashes.size());
         }
     }
+    if (strs) out.ps.finish();
     rs = std::move(out);
     return GPUDIFF_OK;
 }
@@ -679,6 +845,18 @@ DStore* dstore_create(gpudiff_ctx* c, uint32_t max_slots, uint64_t space_bytes, 
 int dstore_submit(gpudiff_ctx* c, DStore* s, const gpudiff_event* ev, size_t n, gpudiff_ticket* ticket) {
     if (s->broken) return GPUDIFF_E_STATE;
     if (n > s->max_events) return GPUDIFF_E_INVAL;
+    if (!s->pair_mode && (c->flags & GPUDIFF_OPT_PATH_STRINGS)) {
+        // The batch in flight renders its paths, at its gpudiff_wait, from the space it was written to.  If a
+        // compaction has since left it behind in the other space, the next compaction packs into that space: a
+        // submit that may need one is refused before it changes anything (wait on the outstanding ticket first).
+        const Ring& O = s->ring[s->ring_next ^ 1u];
+        if (O.outstanding && O.strs && O.space_idx != s->cur) {
+            uint64_t pre = 0;  // >= the bound ensure_space is asked for below
+            for (size_t i = 0; i < n; i++)
+                pre += (5 * ((uint64_t)ev[i].new_len + (ev[i].old_json ? ev[i].old_len : 0))) / 2 + 768;
+            if (s->used_ub + pre > s->space_bytes) return GPUDIFF_E_STATE;
+        }
+    }
     const auto t_host0 = std::chrono::steady_clock::now();
     const bool timing = (c->flags & GPUDIFF_OPT_TIMING) != 0;
     Ring& R = s->ring[s->ring_next];
@@ -938,6 +1116,8 @@ int dstore_submit(gpudiff_ctx* c, DStore* s, const gpudiff_event* ev, size_t n, 
         (rc = grow_dev(&R.dmeta, &R.dmeta_cap, meta_bytes)) || (rc = grow_dev(&R.douts, &R.docs_cap, nd + 1)))
         return rc;
     if ((rc = grow_dev(&R.dcoll, &R.coll_cap, nd + 1)) || (rc = grow_dev(&R.ddef, &R.def_cap, n + 1))) return rc;
+    const bool strs = (c->flags & GPUDIFF_OPT_PATH_STRINGS) != 0;
+    if (strs && (rc = grow_dev(&R.dntab, &R.ntab_cap, 2 * (uint64_t)n + 2))) return rc;
     hipStream_t st = c->stream, cs = s->cs;
     hipStream_t k0s = dec ? s->ks0 : st;  // the K0 stage's stream (even chunks, K0c, K0x)
     if (timing && !R.t_ev[0])
@@ -1052,7 +1232,7 @@ int dstore_submit(gpudiff_ctx* c, DStore* s, const gpudiff_event* ev, size_t n, 
     HIPCHK(hipMemsetAsync(R.dcnt, 0, 4, k0s));
     gpudiff_dbatch* d = R.d;
     HIPCHK(launch_link(k0s, dheads, nh, dlinks, R.douts, R.dcoll, s->slots, d->rows, d->pair_ids, R.ddef, batch,
-                       R.dcnt, s->ctr));
+                       R.dcnt, s->ctr, strs ? R.dntab : nullptr));
     HIPCHK(hipEventRecord(R.k0_done, k0s));
     R.k0_recorded = true;
     if (timing) HIPCHK(hipEventRecord(R.t_ev[4], k0s));
@@ -1081,6 +1261,8 @@ int dstore_submit(gpudiff_ctx* c, DStore* s, const gpudiff_event* ev, size_t n, 
     R.batch = batch;
     R.nev = (uint32_t)n;
     R.bound = bound;
+    R.strs = strs;
+    R.space_idx = s->cur;
     R.ticket = *ticket;
     R.outstanding = true;
     Ring* Rp = &R;
@@ -1112,7 +1294,14 @@ int dstore_submit(gpudiff_ctx* c, DStore* s, const gpudiff_event* ev, size_t n, 
             for (int k = 0; k < 3; k++) s->t_sum[1 + k] += ms[k];
             s->t_n++;
         }
-        int r2 = ndef ? resolve(s, RR, rs) : GPUDIFF_OK;
+        // the strings before resolve(): its compaction may pack into the space this batch's superseded blobs are in
+        int r2 = RR.strs ? render_paths(s, RR, rs) : GPUDIFF_OK;
+        if (!r2 && ndef) r2 = resolve(s, RR, rs);
+        if (!r2 && RR.strs) {
+            s->c->path_stats.paths += rs.ps.n;
+            s->c->path_stats.bytes += rs.ps.offsets()[rs.ps.n];
+            s->c->path_stats.host_paths += rs.ps.n_host;
+        }
         if (r2) s->broken = true;
         if (!r2 && s->pair_mode) {  // kept for gpudiff_write_plan_get
             RR.final_flags.assign(rs.flags.begin(), rs.flags.end());
@@ -1259,8 +1448,11 @@ void dstore_free(gpudiff_ctx* c, DStore* s) {
     for (Ring& R : s->ring) {
         if (R.d) gpudiff_dbatch_free(c, R.d);
         if (R.ticket) c->finishers.erase(R.ticket);
-        for (void* p : {(void*)R.djson, (void*)R.dmeta, (void*)R.douts, (void*)R.dcoll, (void*)R.ddef, (void*)R.dcnt})
+        for (void* p : {(void*)R.djson, (void*)R.dmeta, (void*)R.douts, (void*)R.dcoll, (void*)R.ddef, (void*)R.dcnt,
+                        (void*)R.dntab, (void*)R.ps_len, (void*)R.ps_tiles, (void*)R.ps_ctr, (void*)R.ps_out})
             if (p) (void)hipFree(p);
+        for (auto& e : R.ps_ev)
+            if (e) (void)hipEventDestroy(e);
         for (void* p : {(void*)R.hjson, (void*)R.hmeta})
             if (p) (void)hipHostFree(p);
         if (R.staged) (void)hipEventDestroy(R.staged);

@@ -12,7 +12,9 @@
 //   K0x k_link           lane per slot chain: walks the slot's documents in
 //                        batch order, writes each event's (old, new) row for the
 //                        diff pass or defers the rest of the chain to the host,
-//                        and makes the last encoded version resident
+//                        and makes the last encoded version resident; with
+//                        GPUDIFF_OPT_PATH_STRINGS it also records each row's two
+//                        path-table entry counts for K15 / K16 (paths.hip)
 //   K8  k_slot_sizes / k_scan_* / k_pack_slots   compaction of the live blobs
 //                        into the other space
 //   K9  k_place          host-resolved blobs, rows and slot states
@@ -122,7 +124,8 @@ __global__ __launch_bounds__(256) void k_link(const uint32_t* __restrict__ heads
                                               const uint8_t* __restrict__ coll, DSlot* __restrict__ slots,
                                               gpudiff_pair_row* __restrict__ rows, uint32_t* __restrict__ pair_ids,
                                               uint8_t* __restrict__ deferred, uint32_t batch,
-                                              uint32_t* __restrict__ n_deferred, uint32_t* __restrict__ counters) {
+                                              uint32_t* __restrict__ n_deferred, uint32_t* __restrict__ counters,
+                                              uint32_t* __restrict__ ntab) {
     const uint32_t h = blockIdx.x * blockDim.x + threadIdx.x;
     if (h >= n_heads) return;
     int32_t doc = (int32_t)heads[h];
@@ -175,6 +178,10 @@ __global__ __launch_bounds__(256) void k_link(const uint32_t* __restrict__ heads
         r.stat_ar_b = o.stat_ar;
         r.flags_b = o.oflags | (seed << GPUDIFF_OBJ_SEED_SHIFT);
         rows[L.row] = r;
+        if (ntab) {  // GPUDIFF_OPT_PATH_STRINGS: the tables K15 / K16 walk (paths.hip)
+            ntab[2ull * L.row] = have_a ? A.ntab : 0u;
+            ntab[2ull * L.row + 1] = o.n_tab;
+        }
         A = ref_of(o);
         a_bytes = o.bytes;
         have_a = true;
@@ -365,10 +372,10 @@ hipError_t launch_collide(hipStream_t s, const DocLink* links, const TokOut* out
 hipError_t launch_link(hipStream_t s, const uint32_t* heads, uint32_t n_heads, const DocLink* links,
                        const TokOut* outs, const uint8_t* coll, DSlot* slots, gpudiff_pair_row* rows,
                        uint32_t* pair_ids, uint8_t* deferred, uint32_t batch, uint32_t* n_deferred,
-                       uint32_t* counters) {
+                       uint32_t* counters, uint32_t* ntab) {
     if (!n_heads) return hipSuccess;
     k_link<<<(n_heads + 255) / 256, 256, 0, s>>>(heads, n_heads, links, outs, coll, slots, rows, pair_ids, deferred,
-                                                  batch, n_deferred, counters);
+                                                  batch, n_deferred, counters, ntab);
     return hipGetLastError();
 }
 

@@ -2,6 +2,7 @@
 // store.cpp).  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <string.h>
 
 #include <algorithm>
 #include <array>
@@ -119,11 +120,42 @@ struct gpudiff_dbatch {
 
 struct DStore;
 
+// GPUDIFF_OPT_PATH_STRINGS: the changed paths as text, entry i for hashes[i] / kinds[i].  One allocation, as it
+// comes back from the device in one copy: offsets[n + 1], then the strings' bytes
+struct PathStrs {
+    bool on = false;
+    size_t n = 0;
+    std::vector<uint64_t> words;  // [n + 1] offsets | bytes (rounded up to 8)
+    size_t n_host = 0, n_unresolved = 0;
+    const uint64_t* offsets() const { return words.data(); }
+    const char* bytes() const { return (const char*)(words.data() + n + 1); }
+    // built entry by entry (the host resolution's merge)
+    void begin() {
+        words.assign(1, 0);
+        tail.clear();
+        n = 0;
+    }
+    void push(const char* p, size_t len) {
+        tail.append(p, len);
+        words.push_back(tail.size());
+        n++;
+    }
+    void finish() {
+        const size_t w = (tail.size() + 7) / 8;
+        words.resize(n + 1 + w, 0);
+        if (!tail.empty()) memcpy(words.data() + n + 1, tail.data(), tail.size());
+        tail.clear();
+        tail.shrink_to_fit();
+    }
+    std::string tail;
+};
+
 struct ResultStore {
     std::vector<uint8_t> flags;
     std::vector<uint32_t> spec, status, dirty, off;
     std::vector<uint64_t> hashes;
     std::vector<uint8_t> kinds;
+    PathStrs ps;
 };
 
 struct gpudiff_ctx {
@@ -148,6 +180,7 @@ struct gpudiff_ctx {
     std::unordered_map<gpudiff_ticket, std::function<int(ResultStore&)>> finishers;
     // GPUDIFF_OPT_DEVICE_ENCODE: gpudiff_submit's pairs go through K0 (dstore.cpp, pair mode)
     DStore* pair_store = nullptr;
+    gpudiff_path_stats path_stats{};  // GPUDIFF_OPT_PATH_STRINGS: what the finishers rendered
     // submit ring
     gpudiff_dbatch* ring[2] = {nullptr, nullptr};
     gpudiff_hbatch* ring_hb[2] = {nullptr, nullptr};

@@ -228,11 +228,13 @@ hipError_t launch_negotiate_pairs(hipStream_t s, const NegOut* outs, const uint8
 // K0c: per event, a path-hash collision with its old side (the two path tables disagree)
 hipError_t launch_collide(hipStream_t s, const DocLink* links, const TokOut* outs, const DSlot* slots, uint32_t n,
                           const uint8_t* space, uint8_t* coll);
-// K0x: walk each slot's chain: rows for K2, deferrals, the slot's new resident blob
+// K0x: walk each slot's chain: rows for K2, deferrals, the slot's new resident blob.  ntab (GPUDIFF_OPT_PATH_STRINGS,
+// else null: no store issued): per row, the path-table entry counts of its old and new blob (K15 / K16 need them; a
+// side that does not exist: 0)
 hipError_t launch_link(hipStream_t s, const uint32_t* heads, uint32_t n_heads, const DocLink* links,
                        const TokOut* outs, const uint8_t* coll, DSlot* slots, gpudiff_pair_row* rows,
                        uint32_t* pair_ids, uint8_t* deferred, uint32_t batch, uint32_t* n_deferred,
-                       uint32_t* counters);
+                       uint32_t* counters, uint32_t* ntab = nullptr);
 // compaction: pack every live slot's blob into dst, rewrite the offsets, *used = total
 hipError_t launch_compact_store(hipStream_t s, DSlot* slots, uint32_t n, const uint8_t* src, uint8_t* dst,
                                 uint64_t* sizes, uint64_t* block_sums, unsigned long long* used);
@@ -242,5 +244,30 @@ hipError_t launch_place(hipStream_t s, const uint8_t* stage, uint64_t bytes, uin
                         uint32_t n_rows, const SlotUpdate* ups, uint32_t n_ups, DSlot* slots, uint32_t* counters,
                         uint32_t* err);
 hipError_t launch_forget(hipStream_t s, DSlot* slots, uint32_t slot, uint32_t* counters);
+
+// ------------------------------------------------------------ changed paths as text (paths.hip)
+// One diffed device-encoded batch: its rows and K0x's table counts, the diff pass's changed-path lists
+// (dirty_idx -> row, path_off CSR, out_h / out_k) and the space its blobs live in.
+struct PathJob {
+    const gpudiff_pair_row* rows;
+    const uint32_t* ntab;       // [2 * row + side]
+    const uint32_t* dirty_idx;  // [n_dirty]
+    const uint32_t* path_off;   // [n_dirty + 1]
+    const uint64_t* out_h;      // [n_paths]
+    const uint8_t* out_k;       // [n_paths]
+    const uint8_t* space;
+    uint64_t space_bytes;
+    uint64_t mask;              // the context's path-hash mask (the root's hash is seed & mask)
+    uint32_t n_dirty, n_paths;
+};
+constexpr uint32_t kPathTile = 1024;  // the scan's tile (256 threads x 4)
+inline uint32_t path_tiles(uint32_t n_paths) { return (n_paths + kPathTile - 1) / kPathTile; }
+// K15 k_path_len + the scan's first two steps: lens[n_paths], tile_sums[path_tiles] (exclusive), ctr[0] = the
+// strings' total bytes; ctr[1] (zeroed here) counts unresolved entries
+hipError_t launch_path_len(hipStream_t s, const PathJob& j, uint64_t* lens, uint64_t* tile_sums,
+                           unsigned long long* ctr);
+// the scan's last step (offsets[n_paths + 1]) + K16 k_path_write: string i at bytes[offsets[i], offsets[i + 1])
+hipError_t launch_path_write(hipStream_t s, const PathJob& j, const uint64_t* lens, const uint64_t* tile_sums,
+                             uint64_t* offsets, uint8_t* bytes, uint64_t bytes_cap, unsigned long long* ctr);
 
 }  // namespace gd

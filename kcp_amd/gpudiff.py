@@ -28,6 +28,7 @@ PATH_CHANGED, PATH_ADDED, PATH_REMOVED, PATH_STATUS_ABSENT = 0, 1, 2, 3
 PATH_REGION_STATUS = 0x80
 OPT_TIMING = 0x1
 OPT_DEVICE_ENCODE = 0x2000000
+OPT_PATH_STRINGS = 0x8000000  # device-encoded batches: K15/K16 render the changed paths as text (DiffResult.path_strings)
 OPT_ARENA_SHIFT = 21  # test hook: 4 bits, the K2 wave arenas shrunk 2^k-fold (forces the deferred K4 path)
 DEVICE_CURRENT, DEVICE_NONE = -1, -2
 
@@ -263,6 +264,16 @@ class Result(C.Structure):
                 ("internal_", C.c_void_p)]
 
 
+class PathStringsC(C.Structure):
+    _fields_ = [("n_paths", C.c_size_t), ("offsets", C.c_void_p), ("bytes", C.c_void_p), ("n_host", C.c_size_t),
+                ("n_unresolved", C.c_size_t)]
+
+
+class PathStats(C.Structure):
+    _fields_ = [("batches", C.c_uint64), ("paths", C.c_uint64), ("bytes", C.c_uint64), ("host_paths", C.c_uint64),
+                ("kernel_ms", C.c_double), ("timed_batches", C.c_uint64)]
+
+
 class DeviceView(C.Structure):
     _fields_ = [("pair_flags", C.c_void_p), ("spec_dirty_ids", C.c_void_p), ("status_dirty_ids", C.c_void_p),
                 ("dirty_ids", C.c_void_p), ("counts", C.c_void_p)]
@@ -307,6 +318,8 @@ SIGNATURES = [
     ("gpudiff_diff", C.c_int, [_P, _P, C.POINTER(C.c_uint64)]),
     ("gpudiff_wait", C.c_int, [_P, C.c_uint64, C.POINTER(Result)]),
     ("gpudiff_result_release", None, [_P, C.POINTER(Result)]),
+    ("gpudiff_result_path_strings", C.c_int, [_P, C.POINTER(Result), C.POINTER(PathStringsC)]),
+    ("gpudiff_path_strings_stats_get", C.c_int, [_P, C.POINTER(PathStats)]),
     ("gpudiff_last_timings", C.c_int, [_P, C.POINTER(Timings)]),
     ("gpudiff_sync", C.c_int, [_P]),
     ("gpudiff_timing_reset", C.c_int, [_P]),
@@ -328,6 +341,8 @@ SIGNATURES = [
                                          C.c_size_t, C.c_void_p, C.c_uint64, C.POINTER(ObjInfo)]),
     ("gpudiff_encode_object_host", C.c_int, [C.c_char_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64,
                                              C.POINTER(ObjInfo)]),
+    ("gpudiff_render_path_from_blob", C.c_int, [C.c_char_p, C.POINTER(ObjInfo), C.c_uint32, C.c_uint64, C.c_void_p,
+                                                C.c_size_t, C.POINTER(C.c_size_t)]),
     ("gpudiff_k0_profile", C.c_int, [_P, C.c_int, C.POINTER(C.c_uint64)]),
     ("gpudiff_k2_profile", C.c_int, [_P, C.c_void_p, C.c_uint32]),
     ("gpudiff_upsert_bodies", C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_size_t, C.c_uint32,
@@ -468,11 +483,25 @@ class DiffResult:
     path_offsets: np.ndarray        # u32 [n_dirty + 1]
     path_hashes: np.ndarray         # u64
     path_kinds: np.ndarray          # u8
+    # OPT_PATH_STRINGS on a device-encoded batch: the text of every changed path (raw key bytes), in the order of
+    # path_hashes / path_kinds; None when the engine rendered none (gpudiff_result_path_strings: E_STATE)
+    path_strings: Optional[List[bytes]] = None
+    paths_host: int = 0             # entries the host path rendered (K0's deferrals)
+    paths_unresolved: int = 0       # entries whose table walk failed (empty strings); always 0
 
     def paths_of(self, k: int) -> List[Tuple[int, int]]:
         """[(hash, kind)] of the k-th dirty pair."""
         b, e = int(self.path_offsets[k]), int(self.path_offsets[k + 1])
         return list(zip(self.path_hashes[b:e].tolist(), self.path_kinds[b:e].tolist()))
+
+    def rendered_paths_of(self, k: int) -> List[Tuple[int, int, str]]:
+        """[(hash, kind, path)] of the k-th dirty pair (OPT_PATH_STRINGS); keys that are not UTF-8 keep their
+        bytes as surrogate escapes."""
+        if self.path_strings is None:
+            raise GpuDiffError(E_STATE, "DiffResult.rendered_paths_of")
+        b, e = int(self.path_offsets[k]), int(self.path_offsets[k + 1])
+        return [(h, kd, s.decode("utf-8", "surrogateescape")) for h, kd, s in
+                zip(self.path_hashes[b:e].tolist(), self.path_kinds[b:e].tolist(), self.path_strings[b:e])]
 
 
 def _arr(ptr, n, dtype):
@@ -775,9 +804,24 @@ class Engine:
                 path_offsets=_arr(r.path_offsets, r.n_dirty + 1, np.uint32),
                 path_hashes=_arr(r.path_hashes, r.n_paths, np.uint64),
                 path_kinds=_arr(r.path_kinds, r.n_paths, np.uint8))
+            ps = PathStringsC()
+            rc = _lib.gpudiff_result_path_strings(self.ctx, C.byref(r), C.byref(ps))
+            if rc == OK:
+                offs = _arr(ps.offsets, ps.n_paths + 1, np.uint64).tolist()
+                raw = C.string_at(ps.bytes, offs[-1]) if offs[-1] else b""
+                out.path_strings = [raw[offs[i]:offs[i + 1]] for i in range(ps.n_paths)]
+                out.paths_host, out.paths_unresolved = int(ps.n_host), int(ps.n_unresolved)
+            elif rc != E_STATE:
+                raise GpuDiffError(rc, "gpudiff_result_path_strings")
         finally:
             _lib.gpudiff_result_release(self.ctx, C.byref(r))
         return out
+
+    def path_stats(self) -> PathStats:
+        """gpudiff_path_strings_stats_get: what OPT_PATH_STRINGS rendered so far (kernel_ms with timing)."""
+        st = PathStats()
+        _chk(_lib.gpudiff_path_strings_stats_get(self.ctx, C.byref(st)), "gpudiff_path_strings_stats_get")
+        return st
 
     def sync(self):
         _chk(_lib.gpudiff_sync(self.ctx), "gpudiff_sync")
@@ -1232,6 +1276,25 @@ def resolve_path(old, new, path_hash: int, path_kind: int, path_hash_bits: int =
         _chk(_lib.gpudiff_resolve_path(a, len(a), b, len(b), path_hash, path_kind, path_hash_bits, buf,
                                        n.value + 1, C.byref(n)), "gpudiff_resolve_path")
     return buf.value.decode("utf-8", "replace")
+
+
+def render_path_from_blob(blob: bytes, info, seed: int, path_hash: int) -> bytes:
+    """gpudiff_render_path_from_blob: the text of `path_hash` from one object's blob in the device-store format
+    (encode_object_host / Engine.encode_objects output; info = its dict or ObjInfo).  No GPU needed."""
+    if not isinstance(info, ObjInfo):
+        d, info = info, ObjInfo()
+        for f, _ in ObjInfo._fields_:
+            setattr(info, f, d.get(f, 0))
+    n = C.c_size_t(0)
+    rc = _lib.gpudiff_render_path_from_blob(blob, C.byref(info), seed, path_hash, None, 0, C.byref(n))
+    if rc == OK:
+        return b""
+    if rc != E_CAPACITY:
+        raise GpuDiffError(rc, "gpudiff_render_path_from_blob")
+    buf = C.create_string_buffer(n.value)
+    _chk(_lib.gpudiff_render_path_from_blob(blob, C.byref(info), seed, path_hash, C.cast(buf, C.c_void_p), n.value,
+                                            C.byref(n)), "gpudiff_render_path_from_blob")
+    return buf.raw[:n.value]
 
 
 def encode_object_host(doc, seed: int = 0, path_hash_bits: int = PATH_HASH_BITS):
