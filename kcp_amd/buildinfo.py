@@ -17,8 +17,8 @@ SOURCES = ["kernels.hip", "tokenize.hip", "rollup.hip", "negotiate.hip", "dstore
            "dstore.cpp", "devenc.cpp", "upsert.cpp", "rollup.cpp", "negotiate.cpp", "encoder.cpp", "json.cpp",
            "buildid.cpp"]
 SYNTH_SOURCES = ["synth.cpp", "encoder.cpp", "json.cpp", "buildid.cpp"]
-HEADERS = ["kernels.h", "pool.h", "tokenize.h", "tokdev.h", "marshal_phases.inc", "rollup_phases.inc",
-           "negotiate_phases.inc", "goscan.h", "rollup.h", "ryu_tables.h", "dstore.h", "decfloat.h", "pow10_128.h",
+HEADERS = ["kernels.h", "pool.h", "tokenize.h", "tokdev.h", "marshal_phases.h", "rollup_phases.h",
+           "negotiate_phases.h", "goscan.h", "rollup.h", "ryu_tables.h", "dstore.h", "decfloat.h", "pow10_128.h",
            "encoder.h", "engine.h", "json.h", "xxh64.h", "pathstr.h"]
 MAPS = ["gpudiff.map", "synth.map"]
 INCLUDE_NAMES = ["gpudiff.h", "gpudiff_format.h", "gpudiff_synth.h"]

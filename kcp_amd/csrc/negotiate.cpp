@@ -495,7 +495,7 @@ int gpudiff_nbatch_create_kinds(gpudiff_ctx* c, const uint8_t* kinds, const uint
         t.json_off = jb;
         t.json_len = l;
         t.scratch_off = sb;
-        t.pad[0] = nb->kinds[p];  // K13: which typed status to read
+        tokdoc_set_neg_kind(t, nb->kinds[p]);  // K13: which typed status to read
         if (l <= kTokMaxLen) {
             jb = (jb + l + kTokSlack + 15) & ~15ull;
             sb += rollup_scratch_bytes(l);

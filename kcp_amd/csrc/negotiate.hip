@@ -102,7 +102,7 @@ __global__ __launch_bounds__(256) void k_negotiate_pairs(const NegOut* __restric
         else if (span_eq(da + A.rv_off, A.rv_len, db + B.rv_off, B.rv_len)) act = GPUDIFF_NEG_IGNORE;  // :263-265
         else if (A.gen != B.gen) act = GPUDIFF_NEG_SPEC;                                                 // :267-270
         else if (!status_eq(A, da, B, db) ||
-                 (docs[2u * i + 1u].pad[0] == GPUDIFF_NEG_KIND_CRD && !crd_status_eq(A, da, B, db)))
+                 (tokdoc_neg_kind(docs[2u * i + 1u]) == GPUDIFF_NEG_KIND_CRD && !crd_status_eq(A, da, B, db)))
             act = GPUDIFF_NEG_STATUS;  // :272-275
         else if (!map_eq(A.ann, A.n_ann, da, B.ann, B.n_ann, db) || map_eq(A.lab, A.n_lab, da, B.lab, B.n_lab, db))
             act = GPUDIFF_NEG_META;  // :277-281, the missing `!` before the labels term kept

@@ -1,5 +1,5 @@
-// K13 -- the API-negotiation update classifier's fields,
-// spliced into k_encode_docs<MINW, kModeNegotiate> after phases 1-2 (structural
+// K13 -- the API-negotiation update classifier's fields:
+// what k_encode_docs<MINW, kModeNegotiate> runs after phases 1-2 (structural
 // scan, tree).
 //
 // pkg/reconciler/apiresource/controller.go:253-283 reads, per typed
@@ -16,7 +16,7 @@
 //      kNegMaxConds
 //   N4 condition fields: exact names at most once each, strings without
 //      escapes (or null), lastTransitionTime in neg_parse_time's strict shape
-// For a CustomResourceDefinition (TokDoc.pad[0] == GPUDIFF_NEG_KIND_CRD,
+// For a CustomResourceDefinition (tokdoc_neg_kind() == GPUDIFF_NEG_KIND_CRD,
 // controller.go:186-199) the status also holds acceptedNames and
 // storedVersions:
 //   N2 status.acceptedNames (null / object) and storedVersions (null / array)
@@ -36,20 +36,33 @@
 // order -- root members, their fields, map entries / condition elements / CRD name fields, CRD list elements,
 // condition fields -- each level's parent ids (and kinds) taken by ballot before the next level looks at the chunk.
 // The first N0 error a lane meets stays its code; any N1-N4 failure is GPUDIFF_TOK_FIELD.
-{
-    mark(1);
-    NegOut* const O = (NegOut*)space + doc_i;
+#pragma once
+#include "tokdev.h"
+
+namespace gd {
+
+namespace {
+
+// T: the document's tree; neg_kind: GPUDIFF_NEG_KIND_* (which typed status to read); O: the document's result; lds:
+// the wave's LDS area
+__device__ __forceinline__ void negotiate_doc(const DocTree& T, uint32_t neg_kind, NegOut* O, uint8_t* lds,
+                                              PhaseClock& mark) {
+    const uint8_t* const d = T.d;
+    const uint32_t len = T.len, lane = T.lane, nn = T.nn;
+    const Scratch& S = T.S;
+    uint32_t status = T.status;
+    mark(PS_TREE);
     // LDS (the phase 1-2 areas are free now): label / annotation tables, the
     // condition table, condition element node ids, per (condition, field) counts
-    NegMember* const t_lab = (NegMember*)lds;
-    NegMember* const t_ann = t_lab + kNegMaxMembers;
-    NegCond* const t_cond = (NegCond*)(lds + 512);
-    uint32_t* const t_eid = (uint32_t*)(lds + 512 + 384);
-    uint32_t* const t_cnt = t_eid + kNegMaxConds;
-    NegSpan* const t_short = (NegSpan*)(lds + 1152);  // CRD lists: 3 x kNegMaxList spans
-    NegSpan* const t_cat = t_short + kNegMaxList;
-    NegSpan* const t_stored = t_cat + kNegMaxList;
-    const bool crd = D.pad[0] == GPUDIFF_NEG_KIND_CRD;
+    NegMember* const t_lab = (NegMember*)(lds + kLdsNegLab.off);
+    NegMember* const t_ann = (NegMember*)(lds + kLdsNegAnn.off);
+    NegCond* const t_cond = (NegCond*)(lds + kLdsNegCond.off);
+    uint32_t* const t_eid = (uint32_t*)(lds + kLdsNegEid.off);
+    uint32_t* const t_cnt = (uint32_t*)(lds + kLdsNegCnt.off);
+    NegSpan* const t_short = (NegSpan*)(lds + kLdsNegShort.off);  // CRD lists: 3 x kNegMaxList spans
+    NegSpan* const t_cat = (NegSpan*)(lds + kLdsNegCat.off);
+    NegSpan* const t_stored = (NegSpan*)(lds + kLdsNegStored.off);
+    const bool crd = neg_kind == GPUDIFF_NEG_KIND_CRD;
     // LDS tables start empty (N4 fills condition fields as the sweep meets them)
     if (lane < kNegMaxConds) {
         NegCond z{};
@@ -351,6 +364,9 @@
 #pragma unroll
             for (uint32_t q = 0; q < 4; q++) O->names[q] = names[q];
     }
-    mark(2);
-    return;
+    mark(PN_SWEEP);
 }
+
+}  // namespace
+
+}  // namespace gd

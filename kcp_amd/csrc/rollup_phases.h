@@ -1,6 +1,6 @@
-// K11 -- the Deployment splitter's status roll-up fields,
-// spliced into k_encode_docs<MINW, kModeRollup> after phases 1-2 (structural
-// scan, tree).
+// K11 -- the Deployment splitter's status roll-up fields:
+// what k_encode_docs<MINW, kModeRollup> runs after phases 1-2 (structural scan,
+// tree).
 //
 // pkg/reconciler/deployment/deployment.go:41-91 reads, per cached Deployment,
 // the kcp.dev/owned-by label (the selector at :44-51) and the five int32
@@ -26,8 +26,20 @@
 // (metadata / status ids by ballot), then the members of those (labels), then the members of labels.  (Separate
 // passes paid the record -> token -> bytes chain once per pass and per looked-up node kind.)  The first R0 error a
 // lane meets stays its code; any R1-R3 failure is GPUDIFF_TOK_FIELD, applied in that order.
-{
-    mark(1);  // tuning hook (gpudiff_k0_profile): [0] scan, [1] tree, [2] R0-R3
+#pragma once
+#include "tokdev.h"
+
+namespace gd {
+
+namespace {
+
+// T: the document's tree; out: the document's result
+__device__ __forceinline__ void rollup_doc(const DocTree& T, RollOut* out, PhaseClock& mark) {
+    const uint8_t* const d = T.d;
+    const uint32_t len = T.len, lane = T.lane, nn = T.nn;
+    const Scratch& S = T.S;
+    uint32_t status = T.status;
+    mark(PS_TREE);
     RollOut R{};
     if (status == GPUDIFF_TOK_OK) {
         uint32_t err0 = 0;     // R0, per lane
@@ -137,7 +149,10 @@
         else if (n_own == 1) R.flags = kRollHasLabel;
     }
     R.status = status;
-    if (lane == 0) ((RollOut*)space)[doc_i] = R;
-    mark(2);
-    return;
+    if (lane == 0) *out = R;
+    mark(PR_SWEEP);
 }
+
+}  // namespace
+
+}  // namespace gd

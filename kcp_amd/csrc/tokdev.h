@@ -1,5 +1,7 @@
-// Device helpers shared by K0 (tokenize.hip) and K10 (marshal.hip): wave
-// primitives, Go string/number decoding, XXH64 over virtual word streams.
+// Device helpers of the document kernel k_encode_docs (tokenize.hip: K0 encode, K10 marshal, K11 roll-up, K13
+// negotiate, whose phases live in marshal_phases.h / rollup_phases.h / negotiate_phases.h) and of K12 (rollup.hip):
+// wave primitives, Go string/number decoding, XXH64 over virtual word streams, the per-wave LDS map, the profile
+// slots and what the kernel's front end (scan, tree) hands to a mode's phases (DocTree).
 // Internal; each including TU gets its own copy (anonymous namespace).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -45,6 +47,69 @@ constexpr uint32_t kLdsSort = 384;  // node keys sorted in LDS up to this many (
 constexpr uint32_t kLdsOrder = 768;  // phase 3b's depth order in LDS up to this many nodes (4 B each, behind 2 KiB)
 constexpr uint32_t kLdsHash = 256;   // ... and up to this many nodes their hashes too (order 1 KiB + hashes 2 KiB)
 constexpr uint32_t kRank = 256;      // phase 4 ranks up to this many node keys in LDS (no sort arrays)
+
+// The per-wave LDS map.  One kLdsPerWave area (5 KiB -> 8 workgroups of 4 waves per CU) is reused phase by phase;
+// every region a phase or a mode touches is named here, and the asserts below hold what the code relies on: regions
+// live at the same time do not overlap, and none ends past the area.
+struct LdsSpan {
+    uint32_t off, bytes;
+};
+constexpr bool lds_fits(LdsSpan a) { return a.off + a.bytes <= kLdsPerWave; }
+constexpr bool lds_disjoint(LdsSpan a, LdsSpan b) { return a.off + a.bytes <= b.off || b.off + b.bytes <= a.off; }
+// phase 1 (scan, every mode): the document's bytes in a ring of four 1 KiB chunks
+constexpr LdsSpan kLdsRing{0, 4096};
+// phase 2 (tree, every mode): one 16-byte entry per nesting level (the ring is free by then)
+constexpr LdsSpan kLdsLevels{0, 16 * kMaxDepth};
+// encode, small documents (<= kLdsHash nodes, depth < 32), phases 3a-5: nodes per depth and depth cursors (u32[32]
+// each), a node's hash inputs (uint2), the depth order (u16), the nodes' hashes (u64)
+constexpr LdsSpan kLdsDepthCnt{0, 4 * 32};
+constexpr LdsSpan kLdsDepthCur{kLdsDepthCnt.off + kLdsDepthCnt.bytes, 4 * 32};
+constexpr LdsSpan kLdsHashIn{kLdsDepthCur.off + kLdsDepthCur.bytes, 8 * kLdsHash};
+constexpr LdsSpan kLdsOrder16{kLdsHashIn.off + kLdsHashIn.bytes, 2 * kLdsHash};
+constexpr LdsSpan kLdsHashes{3072, 8 * kLdsHash};
+// phase 3a, any document: a string being decoded is staged behind the hash inputs (order and hashes are written
+// later, in phase 3b)
+constexpr LdsSpan kLdsStage{kLdsOrder16.off, kLdsPerWave - kLdsOrder16.off};
+// phase 3b of the other documents, and marshal's depth sort: nodes per depth and depth cursors (u32[kMaxDepth + 1]
+// each); phase 3b's depth order (u32, up to kLdsOrder nodes; up to kLdsHash nodes it ends before their hashes)
+constexpr LdsSpan kLdsHist{0, 4 * (kMaxDepth + 1)};
+constexpr LdsSpan kLdsCursor{kLdsHist.off + kLdsHist.bytes, 4 * (kMaxDepth + 1)};
+constexpr LdsSpan kLdsOrder32{kLdsCursor.off + kLdsCursor.bytes, 4 * kLdsOrder};
+// phase 4: the rank sort's node order (u16, beside the hash inputs and hashes that phase 5 still reads), or the
+// bitonic sort's keys and node ids (they overwrite kLdsHashes batch by batch behind their reader: see phase 4)
+constexpr LdsSpan kLdsRankIds{kLdsOrder16.off, 2 * kRank};
+constexpr LdsSpan kLdsSortKey{0, 8 * kLdsSort};
+constexpr LdsSpan kLdsSortIdx{kLdsSortKey.off + kLdsSortKey.bytes, 4 * kLdsSort};
+// negotiate (K13): label / annotation tables, the condition table, condition element node ids, per (condition,
+// field) counts, the three CRD string lists
+constexpr LdsSpan kLdsNegLab{0, (uint32_t)sizeof(NegMember) * kNegMaxMembers};
+constexpr LdsSpan kLdsNegAnn{kLdsNegLab.off + kLdsNegLab.bytes, (uint32_t)sizeof(NegMember) * kNegMaxMembers};
+constexpr LdsSpan kLdsNegCond{kLdsNegAnn.off + kLdsNegAnn.bytes, (uint32_t)sizeof(NegCond) * kNegMaxConds};
+constexpr LdsSpan kLdsNegEid{kLdsNegCond.off + kLdsNegCond.bytes, 4 * kNegMaxConds};
+constexpr LdsSpan kLdsNegCnt{kLdsNegEid.off + kLdsNegEid.bytes, 4 * 5 * kNegMaxConds};
+constexpr LdsSpan kLdsNegShort{1152, (uint32_t)sizeof(NegSpan) * kNegMaxList};
+constexpr LdsSpan kLdsNegCat{kLdsNegShort.off + kLdsNegShort.bytes, (uint32_t)sizeof(NegSpan) * kNegMaxList};
+constexpr LdsSpan kLdsNegStored{kLdsNegCat.off + kLdsNegCat.bytes, (uint32_t)sizeof(NegSpan) * kNegMaxList};
+
+static_assert(kLdsRing.bytes == 4096 && kLdsRing.off == 0, "the scan addresses the ring by pos & 4095");
+static_assert(lds_fits(kLdsRing) && lds_fits(kLdsLevels), "phases 1-2");
+static_assert(lds_disjoint(kLdsDepthCnt, kLdsDepthCur) && lds_disjoint(kLdsDepthCur, kLdsHashIn) &&
+                  lds_disjoint(kLdsHashIn, kLdsOrder16) && lds_disjoint(kLdsOrder16, kLdsHashes) &&
+                  lds_disjoint(kLdsHashIn, kLdsHashes) && lds_fits(kLdsHashes),
+              "encode, small documents");
+static_assert(lds_disjoint(kLdsStage, kLdsHashIn) && lds_disjoint(kLdsStage, kLdsDepthCur) && lds_fits(kLdsStage),
+              "phase 3a's staging area");
+static_assert(lds_disjoint(kLdsHist, kLdsCursor) && lds_disjoint(kLdsCursor, kLdsOrder32) && lds_fits(kLdsOrder32) &&
+                  kLdsOrder32.off + 4 * kLdsHash <= kLdsHashes.off,
+              "phase 3b, other documents");
+static_assert(kRank <= kLdsHash && lds_disjoint(kLdsRankIds, kLdsHashIn) && lds_disjoint(kLdsRankIds, kLdsHashes) &&
+                  lds_disjoint(kLdsSortKey, kLdsSortIdx) && lds_fits(kLdsSortIdx),
+              "phase 4");
+static_assert(lds_disjoint(kLdsNegLab, kLdsNegAnn) && lds_disjoint(kLdsNegAnn, kLdsNegCond) &&
+                  lds_disjoint(kLdsNegCond, kLdsNegEid) && lds_disjoint(kLdsNegEid, kLdsNegCnt) &&
+                  lds_disjoint(kLdsNegCnt, kLdsNegShort) && lds_disjoint(kLdsNegShort, kLdsNegCat) &&
+                  lds_disjoint(kLdsNegCat, kLdsNegStored) && lds_fits(kLdsNegStored),
+              "negotiate: tables of kNegMaxMembers, kNegMaxConds and kNegMaxList entries");
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
@@ -1251,6 +1316,72 @@ struct Scratch {
     uint64_t *h, *val, *skey;
     uint32_t *meta, *order, *sidx;
     uint8_t* str;
+};
+// a document's working area for MODE: every mode has tok / rec / str (phases 1-2), only encode the rest
+template <int MODE>
+__device__ __forceinline__ Scratch bind_scratch(uint8_t* base, uint32_t len) {
+    Scratch S{};
+    if constexpr (MODE == kModeRollup || MODE == kModeNegotiate) {
+        S.tok = (uint32_t*)base;
+        S.rec = (uint4*)(base + tok_align(4ull * tok_cap(len)));
+        S.str = base + tok_align(4ull * tok_cap(len)) + tok_align(16ull * node_cap(len));
+    } else if constexpr (MODE == kModeMarshal) {
+        const MarshalLayout ML = marshal_layout(len);
+        S.tok = (uint32_t*)(base + ML.tok);
+        S.rec = (uint4*)(base + ML.rec);
+        S.str = base + ML.str;
+    } else {
+        const TokLayout LY = tok_layout(len);
+        S.tok = (uint32_t*)(base + LY.tok);
+        S.rec = (uint4*)(base + LY.rec);
+        S.h = (uint64_t*)(base + LY.h);
+        S.val = (uint64_t*)(base + LY.val);
+        S.skey = (uint64_t*)(base + LY.skey);
+        S.meta = (uint32_t*)(base + LY.meta);
+        S.order = (uint32_t*)(base + LY.order);
+        S.sidx = (uint32_t*)(base + LY.sidx);
+        S.str = base + LY.str;
+    }
+    return S;
+}
+
+// What the front end (phase 1 scan_tokens, phase 2 build_tree) leaves to a mode's phases: the tokens in S.tok, the
+// node records in S.rec (pre-order, node 0 the root) and these.  status is the front end's verdict; a mode's phases
+// read it and keep their own.
+struct DocTree {
+    const uint8_t* d;  // the document (16-B aligned, kTokSlack bytes readable past len)
+    uint32_t len;
+    uint32_t lane;
+    Scratch S;
+    uint32_t ncap;       // node_cap(len)
+    uint32_t ntok, nn;   // tokens, nodes
+    uint32_t max_depth;
+    uint32_t meta_node, labels_node, annot_node;  // metadata, metadata.labels, metadata.annotations (objects) or NONE
+    bool has_status;
+    bool labels_ok, annot_ok;  // every member of labels / annotations is a string
+    uint32_t status;           // GPUDIFF_TOK_*
+};
+
+// The profiling hook (gpudiff_k0_profile): mark(slot) adds the wall-clock ticks since the previous mark to
+// ticks[slot].  The slots' order is read by position (tools/k0_profile.py, k10_profile.py, k11_profile.py,
+// k13_profile.py, k0_bench.py): it does not change.
+enum FrontSlot : uint32_t { PS_SCAN = 0, PS_TREE = 1 };  // every mode
+enum EncodeSlot : uint32_t { PE_VALUES = 2, PE_HASHES = 3, PE_SORT = 4, PE_BLOB = 5 };  // K0: phases 3a, 3b, 4, 5
+enum MarshalSlot : uint32_t { PM_M1 = 2, PM_M5 = 3, PM_M6_M8 = 4, PM_M9 = 5, PM_M1_FLOATS = 6, PM_M2_M4 = 7 };  // K10
+enum RollupSlot : uint32_t { PR_SWEEP = 2 };  // K11: R0-R3
+enum NegotiateSlot : uint32_t { PN_SWEEP = 2 };  // K13: N0-N4
+struct PhaseClock {
+    unsigned long long* ticks;
+    bool on;
+    uint32_t lane;
+    uint64_t t_prev;
+    __device__ __forceinline__ void operator()(uint32_t slot) {
+        if (on) {
+            const uint64_t t = wall_clock64();
+            if (lane == 0) atomicAdd(&ticks[slot], (unsigned long long)(t - t_prev));
+            t_prev = t;
+        }
+    }
 };
 
 }  // namespace

@@ -38,6 +38,17 @@ struct TokOut {
     uint32_t n_tab;        // path-table entries
 };
 static_assert(sizeof(TokDoc) == 32, "TokDoc");
+// TokDoc.pad by mode.  K10 (marshal): the body's u64 offset in the bodies buffer.  K13 (negotiate): the document's
+// GPUDIFF_NEG_KIND_*.  K0 / K11 leave it unused.
+__host__ __device__ inline void tokdoc_set_marshal_off(TokDoc& t, uint64_t off) {
+    t.pad[0] = (uint32_t)off;
+    t.pad[1] = (uint32_t)(off >> 32);
+}
+__host__ __device__ inline uint64_t tokdoc_marshal_off(const TokDoc& t) {
+    return (uint64_t)t.pad[0] | ((uint64_t)t.pad[1] << 32);
+}
+__host__ __device__ inline void tokdoc_set_neg_kind(TokDoc& t, uint32_t kind) { t.pad[0] = kind; }
+__host__ __device__ inline uint32_t tokdoc_neg_kind(const TokDoc& t) { return t.pad[0]; }
 static_assert(sizeof(TokOut) == 48, "TokOut");
 
 __host__ __device__ inline uint64_t tok_align(uint64_t x) { return (x + 255u) & ~(uint64_t)255u; }
@@ -147,7 +158,7 @@ struct NegOut {
     int64_t pad2;
     NegMember lab[kNegMaxMembers], ann[kNegMaxMembers];
     NegCond cond[kNegMaxConds];
-    // GPUDIFF_NEG_KIND_CRD only (TokDoc.pad[0]): status.acceptedNames {plural,
+    // GPUDIFF_NEG_KIND_CRD only (tokdoc_neg_kind): status.acceptedNames {plural,
     // singular, kind, listKind} (absent / null: empty spans), shortNames,
     // categories, storedVersions (nil and empty: 0 elements)
     NegSpan names[4];
@@ -207,7 +218,7 @@ hipError_t k0_profile(int enable, uint64_t* out8);
 hipError_t launch_encode_docs(hipStream_t s, const TokDoc* docs, uint32_t n, const uint8_t* json, uint8_t* scratch,
                               uint8_t* space, uint64_t space_cap, unsigned long long* used, uint64_t mask,
                               TokOut* out, const DSlot* slots = nullptr, const DocLink* links = nullptr);
-// K10: the write path's request bodies (GPUDIFF_UPSERT_*): docs[i].pad holds
+// K10: the write path's request bodies (GPUDIFF_UPSERT_*): tokdoc_marshal_off(docs[i]) is
 // the body's u64 offset in `bodies` (room: marshal_out_cap(json_len)); out[i]
 // gets {off, bytes, status}.  A nonzero status leaves the document to the host.
 hipError_t launch_marshal_docs(hipStream_t s, const TokDoc* docs, uint32_t n, const uint8_t* json, uint8_t* scratch,

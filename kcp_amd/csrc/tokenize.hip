@@ -31,6 +31,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/gpudiff.h"
 #include "decfloat.h"
 #include "tokenize.h"
@@ -38,100 +40,32 @@
 
 #include "tokdev.h"
 
+#include "marshal_phases.h"
+#include "negotiate_phases.h"
+#include "rollup_phases.h"
+
 namespace gd {
 
 // tuning hook (gpudiff_k0_profile): per-phase wall-clock ticks summed over waves
 __device__ unsigned long long g_k0_prof[8];
 __device__ int g_k0_prof_on;
 
-template <int MINW, int MODE = kModeEncode>
-__global__ __launch_bounds__(256, MINW) void k_encode_docs(const TokDoc* __restrict__ docs, uint32_t n_docs,
-                                                     const uint8_t* __restrict__ json, uint8_t* __restrict__ scratch,
-                                                     uint8_t* __restrict__ space, uint64_t space_cap,
-                                                     unsigned long long* __restrict__ used, uint64_t mask,
-                                                     TokOut* __restrict__ out, const DSlot* __restrict__ slots,
-                                                     const DocLink* __restrict__ links) {
-    // per wave, one LDS area reused phase by phase (5 KiB -> 8 workgroups of 4 waves per CU):
-    //   phase 1: [0, 2048) byte ring; phase 2: [2048, 4096) container stack;
-    //   phases 3a-3b, small documents (<= kLdsHash nodes, depth < 32): [0, 256) depth histogram + cursors,
-    //   [256, 2304) the nodes' hash inputs, [2304, 2816) depth order (u16), [3072, 5120) hashes; phase 3a's decoded
-    //   strings staged at [2304, 5120) after its loop;
-    //   phase 3b, other documents: [0, 2048) depth histogram + cursors, [2048, ..) depth order (<= kLdsOrder nodes);
-    //   phase 4: [0, 4608) sort (ns <= kLdsSort)
-    __shared__ __attribute__((aligned(16))) uint8_t s_lds[kWavesPerBlock][kLdsPerWave];
+namespace {
 
-    const uint32_t lane = lane_id();
-    const uint32_t wib = threadIdx.x >> 6;
-    const uint32_t doc_i = __builtin_amdgcn_readfirstlane(blockIdx.x * kWavesPerBlock + wib);
-    if (doc_i >= n_docs) return;
-    uint8_t* lds = s_lds[wib];
-    uint32_t* hist = (uint32_t*)lds;
-    uint32_t* cur = (uint32_t*)(lds + 1024);
-
-    const TokDoc D = docs[doc_i];
-    const uint8_t* d = json + D.json_off;
-    const uint32_t len = D.json_len;
-    TokOut o{};
-    if (len > kTokMaxLen) {
-        if (lane == 0) {
-            if constexpr (MODE == kModeRollup) {
-                RollOut R{};
-                R.status = GPUDIFF_TOK_SIZE;
-                ((RollOut*)space)[doc_i] = R;
-            } else if constexpr (MODE == kModeNegotiate) {
-                ((NegOut*)space)[doc_i].status = GPUDIFF_TOK_SIZE;
-            } else {
-                o.status = GPUDIFF_TOK_SIZE;
-                out[doc_i] = o;
-            }
-        }
-        return;
-    }
-    uint8_t* base = scratch + D.scratch_off;
-    Scratch S;
-    if constexpr (MODE == kModeRollup || MODE == kModeNegotiate) {
-        S = Scratch{};
-        S.tok = (uint32_t*)base;
-        S.rec = (uint4*)(base + tok_align(4ull * tok_cap(len)));
-        S.str = base + tok_align(4ull * tok_cap(len)) + tok_align(16ull * node_cap(len));
-    } else if constexpr (MODE == kModeMarshal) {
-        const MarshalLayout ML = marshal_layout(len);
-        S = Scratch{};
-        S.tok = (uint32_t*)(base + ML.tok);
-        S.rec = (uint4*)(base + ML.rec);
-        S.str = base + ML.str;
-    } else {
-        const TokLayout LY = tok_layout(len);
-        S.tok = (uint32_t*)(base + LY.tok);
-        S.rec = (uint4*)(base + LY.rec);
-        S.h = (uint64_t*)(base + LY.h);
-        S.val = (uint64_t*)(base + LY.val);
-        S.skey = (uint64_t*)(base + LY.skey);
-        S.meta = (uint32_t*)(base + LY.meta);
-        S.order = (uint32_t*)(base + LY.order);
-        S.sidx = (uint32_t*)(base + LY.sidx);
-        S.str = base + LY.str;
-    }
-    const uint32_t ncap = node_cap(len);
+// ------------------------------------------------------------ phase 1: structural scan
+// One byte per lane per 64-byte step.  Byte classes are VALU compares (their
+// ballots are the step's masks), the in-string state is the parity of an
+// mbcnt of unescaped quotes, token codes are chosen per lane without
+// branches.  The document sits in a 4 x 1 KiB LDS ring: up to 4 KiB is
+// staged in one go; past that, chunk ch + 1 (the lookahead of chunk ch) is
+// written from registers loaded one chunk earlier, so no step waits on HBM.
+// Reads T.d / len / lane and T.S.tok's place; leaves the tokens in T.S.tok, T.ntok and T.status.
+__device__ __forceinline__ void scan_tokens(DocTree& T, uint8_t* lds) {
+    const uint8_t* const d = T.d;
+    const uint32_t len = T.len, lane = T.lane;
+    const Scratch& S = T.S;
     uint32_t status = GPUDIFF_TOK_OK;
-
-    const bool prof = g_k0_prof_on != 0;
-    uint64_t t_prev = prof ? wall_clock64() : 0;
-    auto mark = [&](int ph) {
-        if (prof) {
-            const uint64_t t = wall_clock64();
-            if (lane == 0) atomicAdd(&g_k0_prof[ph], (unsigned long long)(t - t_prev));
-            t_prev = t;
-        }
-    };
-    // ------------------------------------------------------------ phase 1: structural scan
-    // One byte per lane per 64-byte step.  Byte classes are VALU compares (their
-    // ballots are the step's masks), the in-string state is the parity of an
-    // mbcnt of unescaped quotes, token codes are chosen per lane without
-    // branches.  The document sits in a 4 x 1 KiB LDS ring: up to 4 KiB is
-    // staged in one go; past that, chunk ch + 1 (the lookahead of chunk ch) is
-    // written from registers loaded one chunk earlier, so no step waits on HBM.
-    uint8_t* ring = lds;
+    uint8_t* ring = lds + kLdsRing.off;
     uint32_t ntok = 0;
     uint64_t esc_carry = 0, atom_carry = 0;
     uint32_t str_par = 0;
@@ -337,22 +271,32 @@ __global__ __launch_bounds__(256, MINW) void k_encode_docs(const TokDoc* __restr
     if (str_par) status = GPUDIFF_TOK_SYNTAX;  // unterminated string
     if (ctl_in_string && status == GPUDIFF_TOK_OK) status = GPUDIFF_TOK_STRING;
     wave_sync();
+    T.ntok = ntok;
+    T.status = status;
+}
 
-    mark(0);
-    // ------------------------------------------------------------ phase 2: tree building
-    // Lane per token, 64 tokens per batch.  A token's level (containers open
-    // before it) is an mbcnt of opens minus closes; its enclosing container is
-    // the last open one level up before it: found with a ballot per level
-    // present in the batch, or carried from earlier batches in a per-level LDS
-    // table.  A quote is a key when the token two after it is ':' (lookahead),
-    // so node ids are a ballot prefix count and every lane checks its token
-    // against its predecessor on its own (the first failing token decides the
-    // status, as the sequential grammar would stop there).
+// ------------------------------------------------------------ phase 2: tree building
+// Lane per token, 64 tokens per batch.  A token's level (containers open
+// before it) is an mbcnt of opens minus closes; its enclosing container is
+// the last open one level up before it: found with a ballot per level
+// present in the batch, or carried from earlier batches in a per-level LDS
+// table.  A quote is a key when the token two after it is ':' (lookahead),
+// so node ids are a ballot prefix count and every lane checks its token
+// against its predecessor on its own (the first failing token decides the
+// status, as the sequential grammar would stop there).
+// Reads the tokens; leaves the node records in T.S.rec (encode mode: each node's key span and value positions in
+// T.S.skey / T.S.val too, for phase 3a) and the rest of T.
+template <int MODE>
+__device__ __forceinline__ void build_tree(DocTree& T, uint8_t* lds) {
+    const uint32_t lane = T.lane, ncap = T.ncap, ntok = T.ntok;
+    const Scratch& S = T.S;
+    uint32_t status = T.status;
     struct LvlEnt {
         uint32_t id, info, base, cnt1;  // last open at this level: node id, kind/region/flags, level+1 nodes
                                         // before it; level+1 nodes so far
     };
-    LvlEnt* const lvt = (LvlEnt*)lds;  // kMaxDepth entries (4080 B; the ring is free now)
+    static_assert(sizeof(LvlEnt) * kMaxDepth == kLdsLevels.bytes, "the level table's LDS region");
+    LvlEnt* const lvt = (LvlEnt*)(lds + kLdsLevels.off);  // kMaxDepth entries (the ring is free now)
     constexpr uint32_t LF_ARR = 1u, LF_META = 16u, LF_LAB = 32u, LF_ANN = 64u;  // info: is_arr | reg << 1 | flags
     uint32_t nn = 0;
     uint32_t meta_node = NONE, labels_node = NONE, annot_node = NONE;
@@ -538,51 +482,79 @@ __global__ __launch_bounds__(256, MINW) void k_encode_docs(const TokDoc* __restr
         if (status == GPUDIFF_TOK_OK && (ntok == 0u || lvl_c != 0)) status = GPUDIFF_TOK_SYNTAX;
     }
     wave_sync();
+    T.nn = nn;
+    T.max_depth = max_depth;
+    T.meta_node = meta_node;
+    T.labels_node = labels_node;
+    T.annot_node = annot_node;
+    T.has_status = has_status;
+    T.labels_ok = labels_ok;
+    T.annot_ok = annot_ok;
+    T.status = status;
+}
 
-    if constexpr (MODE == kModeMarshal) {
-#include "marshal_phases.inc"
-    }
-    if constexpr (MODE == kModeRollup) {
-#include "rollup_phases.inc"
-    }
-    if constexpr (MODE == kModeNegotiate) {
-#include "negotiate_phases.inc"
-    }
-
-    const uint64_t seed = slots ? ((slots[links[doc_i].slot].flags >> 8) & 0xFFu) : D.seed;
-    mark(1);
-    // which leaves the blob encodes, and which nodes its path table lists (phases 3a and 5)
-    auto region_of = [&](uint32_t w) -> uint32_t {  // 1 spec, 2 status, 0 not encoded (selects, no branches)
+// which leaves the blob encodes, and which nodes its path table lists (phases 3a and 5)
+struct Regions {
+    uint32_t meta_node, labels_node, annot_node;
+    bool labels_ok, annot_ok;
+    // path-table nodes: the region leaves and their ancestors but the root -- every container of the spec / status
+    // subtrees, and metadata, metadata.labels and metadata.annotations when label / annotation leaves are encoded
+    bool lab_in, ann_in, meta_in;
+    __device__ __forceinline__ uint32_t region_of(uint32_t w) const {  // 1 spec, 2 status, 0 not encoded (selects, no
+                                                                       // branches)
         const uint32_t reg = (w >> NI_REG_SHIFT) & 7u;
         const bool sp = (reg == R_SPEC) | ((reg == R_LABELS) & labels_ok) | ((reg == R_ANNOT) & annot_ok);
         const uint32_t r = sp ? 1u : reg == R_STATUS ? 2u : 0u;
         return (w & NI_LEAF) ? r : 0u;
-    };
-    // path-table nodes: the region leaves and their ancestors but the root -- every container of the spec / status
-    // subtrees, and metadata, metadata.labels and metadata.annotations when label / annotation leaves are encoded
-    const bool lab_in = status == GPUDIFF_TOK_OK && labels_node != NONE && labels_ok && !(S.rec[labels_node].w & NI_LEAF);
-    const bool ann_in = status == GPUDIFF_TOK_OK && annot_node != NONE && annot_ok && !(S.rec[annot_node].w & NI_LEAF);
-    const bool meta_in = lab_in || ann_in;
-    auto in_tab = [&](uint32_t i, uint32_t w) -> bool {
+    }
+    __device__ __forceinline__ bool in_tab(uint32_t i, uint32_t w) const {
         const uint32_t reg = (w >> NI_REG_SHIFT) & 7u;
         return (region_of(w) != 0u) | (!(w & NI_LEAF) & ((reg == R_SPEC) | (reg == R_STATUS))) |
                ((i == meta_node) & meta_in) | ((i == labels_node) & lab_in) | ((i == annot_node) & ann_in);
-    };
+    }
+};
+__device__ __forceinline__ Regions bind_regions(const DocTree& T) {
+    Regions G;
+    G.meta_node = T.meta_node;
+    G.labels_node = T.labels_node;
+    G.annot_node = T.annot_node;
+    G.labels_ok = T.labels_ok;
+    G.annot_ok = T.annot_ok;
+    G.lab_in = T.status == GPUDIFF_TOK_OK && T.labels_node != NONE && T.labels_ok &&
+               !(T.S.rec[T.labels_node].w & NI_LEAF);
+    G.ann_in = T.status == GPUDIFF_TOK_OK && T.annot_node != NONE && T.annot_ok && !(T.S.rec[T.annot_node].w & NI_LEAF);
+    G.meta_in = G.lab_in || G.ann_in;
+    return G;
+}
+
+// what phase 3a leaves to phases 3b-5, beside the values in T.S.val / T.S.meta
+struct LeafPlan {
     // phase 5's sizes: spec / status leaves, their arena bytes, path-table nodes and their key bytes
-    uint32_t n_ls = 0, n_lt = 0, n_as = 0, n_at = 0, n_nt = 0, n_kb = 0;
+    uint32_t n_ls, n_lt, n_as, n_at, n_nt, n_kb;
     // small documents: phase 3a also counts the nodes per depth and leaves each node's hash inputs in LDS (key bytes'
     // offset or array index; parent, depth, key length), so phase 3b orders and hashes them without reloading records
-    bool small = nn <= kLdsHash && max_depth < 32u;
-    uint32_t* const h32 = (uint32_t*)lds;           // nodes per depth
-    uint32_t* const c32 = (uint32_t*)(lds + 128);   // depth cursors
+    bool small;
+    uint32_t* h32;  // nodes per depth
+    uint32_t* c32;  // depth cursors
     // hin: x = key offset or index; y = parent | depth << 8 | key << 13 | region << 14 | klen << 16 | path-table
     // node << 21 | string << 22 | decoded string << 23
-    uint2* const hin = (uint2*)(lds + 256);
-    uint16_t* const ord16 = (uint16_t*)(lds + 2304);
-    constexpr uint32_t kStage = 2304;               // phase 3a's decoded strings are staged from here
+    uint2* hin;
+    uint16_t* ord16;  // phase 3b's depth order
+    uint64_t* hl;     // phase 3b's hashes (up to kLdsHash nodes)
+};
+
+// ------------------------------------------------------------ phase 3a: values (lane per node)
+// Decodes every leaf's value into T.S.val / T.S.meta; an error becomes status.
+__device__ __forceinline__ LeafPlan encode_values(const DocTree& T, const Regions& G, uint8_t* lds, uint32_t& status) {
+    const uint8_t* const d = T.d;
+    const uint32_t len = T.len, lane = T.lane, nn = T.nn, ncap = T.ncap;
+    const Scratch& S = T.S;
+    uint32_t n_ls = 0, n_lt = 0, n_as = 0, n_at = 0, n_nt = 0, n_kb = 0;
+    bool small = nn <= kLdsHash && T.max_depth < 32u;
+    uint32_t* const h32 = (uint32_t*)(lds + kLdsDepthCnt.off);
+    uint2* const hin = (uint2*)(lds + kLdsHashIn.off);
     if (small && lane < 32u) h32[lane] = 0u;
     lds_order();
-    // ------------------------------------------------------------ phase 3a: values (lane per node)
     if (status == GPUDIFF_TOK_OK) {
         uint32_t err = GPUDIFF_TOK_OK, nslow = 0, natom = 0;
         // two dependent rounds of loads per 64 nodes, each issued for every lane before any is waited for: the
@@ -602,8 +574,8 @@ __global__ __launch_bounds__(256, MINW) void k_encode_docs(const TokDoc* __restr
             const uint4 r0 = S.rec[ii];
             const uint64_t ks = S.skey[ii], pv = S.val[ii];  // the tree phase's key span and value positions
             const uint4 r = live ? r0 : make_uint4(0u, 0u, 0u, 0u);
-            const uint32_t rg = live ? region_of(r.w) : 0u;
-            const bool tb = live & in_tab(i, r.w);
+            const uint32_t rg = live ? G.region_of(r.w) : 0u;
+            const bool tb = live & G.in_tab(i, r.w);
             const bool key = live & ((r.y & KEYBIT) != 0u), leaf = live & ((r.w & NI_LEAF) != 0u);
             const bool str = leaf & ((r.w & NI_STR) != 0u), atom = leaf & ((r.w & NI_ATOM) != 0u);
             const bool slow = str & ((r.w & NI_SLOW) != 0u);
@@ -695,11 +667,11 @@ __global__ __launch_bounds__(256, MINW) void k_encode_docs(const TokDoc* __restr
             const uint32_t ob = (raw + 16u) & ~15u;  // the decoded bytes' offset in the staging area (<= raw of them)
             int dl;
             uint64_t h8 = 0;
-            if (ob + raw + 16u <= kLdsPerWave - kStage) {
+            if (ob + raw + 16u <= kLdsStage.bytes) {
                 // the raw bytes and the closing quote into LDS (16 B a lane, up to 1 KiB a step; a \u escape never
                 // reads past the quote: its fourth digit position holds it), unescaped there by lane 0, then the
                 // decoded bytes copied out by the wave
-                uint8_t* const st = lds + kStage;
+                uint8_t* const st = lds + kLdsStage.off;
                 const uint8_t* const sp = d + sop + 1;
                 for (uint32_t o = 16u * lane; o < raw + 1u; o += 1024u) {
                     const uint64_t a0 = ld8u(sp + o), a1 = ld8u(sp + o + 8u);
@@ -772,15 +744,29 @@ __global__ __launch_bounds__(256, MINW) void k_encode_docs(const TokDoc* __restr
         const uint32_t e = wave_max(err);  // any error: SYNTAX < NUMBER < ... all nonzero
         if (e) status = e;
     }
+    return LeafPlan{n_ls, n_lt, n_as, n_at, n_nt, n_kb, small, h32, (uint32_t*)(lds + kLdsDepthCur.off), hin,
+                    (uint16_t*)(lds + kLdsOrder16.off), (uint64_t*)(lds + kLdsHashes.off)};
+}
 
-    mark(2);
-    // ------------------------------------------------------------ phase 3b: path hashes by depth
-    // nodes counting-sorted by depth (the order in LDS up to kLdsOrder nodes), then level by level a lane per
-    // node: its record and key span (phase 3a) in one round trip, its parent's hash and its key bytes in the next
-    // Up to kLdsHash nodes their hashes stay in LDS too (behind the order): a level reads its parents' hashes there,
-    // with no fence on the global stores between levels
+// ------------------------------------------------------------ phase 3b: path hashes by depth
+// nodes counting-sorted by depth (the order in LDS up to kLdsOrder nodes), then level by level a lane per
+// node: its record and key span (phase 3a) in one round trip, its parent's hash and its key bytes in the next
+// Up to kLdsHash nodes their hashes stay in LDS too (behind the order): a level reads its parents' hashes there,
+// with no fence on the global stores between levels
+// Leaves the nodes' hashes in P.hl (up to kLdsHash nodes) and, but for small documents, in T.S.h.
+__device__ __forceinline__ void hash_paths(const DocTree& T, const LeafPlan& P, uint8_t* lds, uint64_t seed,
+                                           uint32_t status) {
+    const uint8_t* const d = T.d;
+    const uint32_t len = T.len, lane = T.lane, nn = T.nn, max_depth = T.max_depth;
+    const Scratch& S = T.S;
+    const bool small = P.small;
+    uint32_t *const h32 = P.h32, *const c32 = P.c32;
+    uint2* const hin = P.hin;
+    uint16_t* const ord16 = P.ord16;
+    uint32_t* const hist = (uint32_t*)(lds + kLdsHist.off);
+    uint32_t* const cur = (uint32_t*)(lds + kLdsCursor.off);
     const bool h_in_lds = nn <= kLdsHash;
-    uint64_t* const hl = (uint64_t*)(lds + 2048 + 4 * kLdsHash);
+    uint64_t* const hl = P.hl;
     if (status == GPUDIFF_TOK_OK && nn > 1 && small) {
         // small documents: everything but the key bytes is in LDS -- the depth order from phase 3a's counts, then
         // level by level a lane per node: its inputs and its parent's hash from LDS, its key bytes from the JSON
@@ -864,7 +850,7 @@ __global__ __launch_bounds__(256, MINW) void k_encode_docs(const TokDoc* __restr
         }
         wave_sync();  // phases 4-5 read S.h
     } else if (status == GPUDIFF_TOK_OK && nn > 1) {
-        uint32_t* order = nn - 1 <= kLdsOrder ? (uint32_t*)(lds + 2048) : S.order;
+        uint32_t* order = nn - 1 <= kLdsOrder ? (uint32_t*)(lds + kLdsOrder32.off) : S.order;
         // counting sort of nodes by depth
         for (uint32_t i = lane; i <= kMaxDepth; i += 64) hist[i] = 0;
         wave_sync();
@@ -912,16 +898,30 @@ __global__ __launch_bounds__(256, MINW) void k_encode_docs(const TokDoc* __restr
         }
         wave_sync();  // phases 4-5 read S.h
     }
+}
 
-    mark(3);
-    // ------------------------------------------------------------ phase 4: sort keys, uniqueness
+// what phase 4 leaves to phase 5: the nodes in key order
+struct SortOrder {
+    uint32_t ns;      // every node but the root
+    bool rk;          // ranked: the order is ids16; else sidx, with the keys in skey
+    uint64_t* skey;
+    uint32_t* sidx;
+    uint16_t* ids16;
+};
+// ------------------------------------------------------------ phase 4: sort keys, uniqueness
+__device__ __forceinline__ SortOrder sort_keys(const DocTree& T, const LeafPlan& P, uint8_t* lds, uint64_t seed,
+                                               uint64_t mask, uint32_t& status) {
+    const uint32_t lane = T.lane, nn = T.nn;
+    const Scratch& S = T.S;
+    const bool h_in_lds = nn <= kLdsHash;
+    uint64_t* const hl = P.hl;
     const uint32_t ns = nn > 1 ? nn - 1 : 0;  // every node but the root
-    uint64_t* skey = ns <= kLdsSort ? (uint64_t*)lds : S.skey;
-    uint32_t* sidx = ns <= kLdsSort ? (uint32_t*)(lds + 8 * kLdsSort) : S.sidx;
+    uint64_t* skey = ns <= kLdsSort ? (uint64_t*)(lds + kLdsSortKey.off) : S.skey;
+    uint32_t* sidx = ns <= kLdsSort ? (uint32_t*)(lds + kLdsSortIdx.off) : S.sidx;
     // up to kRank nodes: ranked straight from phase 3b's hashes in LDS into a u16 node order (the node records and
     // hash inputs stay in LDS for phase 5); more: the keys sorted with their node ids
     const bool rk = ns <= kRank && h_in_lds;  // (the hashes must be in LDS: nn <= kLdsHash)
-    uint16_t* const ids16 = (uint16_t*)(lds + 2304);
+    uint16_t* const ids16 = (uint16_t*)(lds + kLdsRankIds.off);
     if (status == GPUDIFF_TOK_OK && ns) {
         const uint64_t root = seed & mask;
         if (rk) {
@@ -969,11 +969,28 @@ __global__ __launch_bounds__(256, MINW) void k_encode_docs(const TokDoc* __restr
             if (ballot(dup)) status = GPUDIFF_TOK_HASH;
         }
     }
+    return SortOrder{ns, rk, skey, sidx, ids16};
+}
 
-    mark(4);
-    // ------------------------------------------------------------ phase 5: blob + path table
+// ------------------------------------------------------------ phase 5: blob + path table
+// space / space_cap / used: the blob space and its append point; o: the document's result but its status
+__device__ __forceinline__ void write_blob(const DocTree& T, const Regions& G, const LeafPlan& P, const SortOrder& O,
+                                           uint64_t seed, uint64_t mask, uint8_t* space, uint64_t space_cap,
+                                           unsigned long long* used, TokOut& o, uint32_t& status) {
+    const uint8_t* const d = T.d;
+    const uint32_t lane = T.lane, nn = T.nn;
+    const Scratch& S = T.S;
+    const uint32_t n_ls = P.n_ls, n_lt = P.n_lt, n_as = P.n_as, n_at = P.n_at, n_nt = P.n_nt, n_kb = P.n_kb;
+    const bool small = P.small, h_in_lds = nn <= kLdsHash;
+    const uint2* const hin = P.hin;
+    const uint64_t* const hl = P.hl;
+    const uint32_t ns = O.ns;
+    const bool rk = O.rk;
+    const uint64_t* const skey = O.skey;
+    const uint32_t* const sidx = O.sidx;
+    const uint16_t* const ids16 = O.ids16;
     o.n_nodes = nn;
-    o.oflags = has_status ? GPUDIFF_OBJ_HAS_STATUS : 0u;
+    o.oflags = T.has_status ? GPUDIFF_OBJ_HAS_STATUS : 0u;
     if (status == GPUDIFF_TOK_OK) {
         // the sizes counted in phase 3a (sums over the nodes: the sort order does not change them)
         const uint32_t Ls = n_ls, Lt = n_lt, Nt = n_nt, KB = n_kb;
@@ -1036,8 +1053,8 @@ __global__ __launch_bounds__(256, MINW) void k_encode_docs(const TokDoc* __restr
                 } else if (j < ns) {
                     i = rk ? ids16[j] : sidx[j];
                     const uint4 r = S.rec[i];
-                    rg = region_of(r.w);
-                    t = in_tab(i, r.w);
+                    rg = G.region_of(r.w);
+                    t = G.in_tab(i, r.w);
                     isk = (r.y & KEYBIT) != 0u;
                     dec = (r.w & NI_SLOW) != 0u;
                     idx = r.y;
@@ -1125,31 +1142,120 @@ __global__ __launch_bounds__(256, MINW) void k_encode_docs(const TokDoc* __restr
             o.n_tab = Nt;
         }
     }
-#if defined(K0_PROBE_VALU) || defined(K0_PROBE_SALU)
-    // timing-only builds (tools/sessions: the marginal cost of a vector / scalar instruction per document): 1024
-    // extra instructions of one kind per document, 8 per iteration of a scalar loop
-    {
-        uint32_t pa = lane ^ status, pb = nn;
-        uint32_t sa = __builtin_amdgcn_readfirstlane(pa), sb = __builtin_amdgcn_readfirstlane(pb);
-        (void)sb;
-        for (uint32_t q = 0; q < 128u + (nn >> 30); q++) {
-#if defined(K0_PROBE_VALU)
-            __asm__ volatile("v_add_u32 %0, %0, %1\n v_add_u32 %0, %0, %1\n v_add_u32 %0, %0, %1\n v_add_u32 %0, %0, %1\n"
-                             "v_add_u32 %0, %0, %1\n v_add_u32 %0, %0, %1\n v_add_u32 %0, %0, %1\n v_add_u32 %0, %0, %1"
-                             : "+v"(pa) : "v"(pb));
-#else
-            __asm__ volatile("s_mov_b32 %0, %1\n s_mov_b32 %0, %1\n s_mov_b32 %0, %1\n s_mov_b32 %0, %1\n"
-                             "s_mov_b32 %0, %1\n s_mov_b32 %0, %1\n s_mov_b32 %0, %1\n s_mov_b32 %0, %1"
-                             : "+s"(sa) : "s"(sb));
-#endif
-        }
-        if ((pa ^ sa) == 0x9E3779B9u) o.n_nodes ^= 0x80000000u;  // never taken in practice: keeps the chains live
-    }
-#endif
-    o.status = status;
-    if (lane == 0) out[doc_i] = o;
-    mark(5);
 }
+
+#if defined(K0_PROBE_VALU) || defined(K0_PROBE_SALU)
+// timing-only builds (tools/sessions: the marginal cost of a vector / scalar instruction per document): 1024
+// extra instructions of one kind per document, 8 per iteration of a scalar loop
+__device__ __forceinline__ void probe_instructions(uint32_t lane, uint32_t status, uint32_t nn, TokOut& o) {
+    uint32_t pa = lane ^ status, pb = nn;
+    uint32_t sa = __builtin_amdgcn_readfirstlane(pa), sb = __builtin_amdgcn_readfirstlane(pb);
+    (void)sb;
+    for (uint32_t q = 0; q < 128u + (nn >> 30); q++) {
+#if defined(K0_PROBE_VALU)
+        __asm__ volatile("v_add_u32 %0, %0, %1\n v_add_u32 %0, %0, %1\n v_add_u32 %0, %0, %1\n v_add_u32 %0, %0, %1\n"
+                         "v_add_u32 %0, %0, %1\n v_add_u32 %0, %0, %1\n v_add_u32 %0, %0, %1\n v_add_u32 %0, %0, %1"
+                         : "+v"(pa) : "v"(pb));
+#else
+        __asm__ volatile("s_mov_b32 %0, %1\n s_mov_b32 %0, %1\n s_mov_b32 %0, %1\n s_mov_b32 %0, %1\n"
+                         "s_mov_b32 %0, %1\n s_mov_b32 %0, %1\n s_mov_b32 %0, %1\n s_mov_b32 %0, %1"
+                         : "+s"(sa) : "s"(sb));
+#endif
+    }
+    if ((pa ^ sa) == 0x9E3779B9u) o.n_nodes ^= 0x80000000u;  // never taken in practice: keeps the chains live
+}
+#endif
+
+// `space` by mode: the blob space (K0), the bodies buffer (K10), RollOut[n] (K11), NegOut[n] (K13); a document's
+// result is out[i] in the first two and space's element i in the others.  The only casts of `space`.
+template <int MODE>
+__device__ __forceinline__ auto* result_of(uint8_t* space, TokOut* out, uint32_t doc_i) {
+    if constexpr (MODE == kModeRollup) return (RollOut*)space + doc_i;
+    else if constexpr (MODE == kModeNegotiate) return (NegOut*)space + doc_i;
+    else return out + doc_i;
+}
+// a document the phases never ran on: only its status
+template <class Out>
+__device__ __forceinline__ void write_status(Out* res, uint32_t status) {
+    if constexpr (std::is_same<Out, NegOut>::value) {
+        res->status = status;
+    } else {
+        Out R{};
+        R.status = status;
+        *res = R;
+    }
+}
+
+}  // namespace
+
+// One wave per document: scan and tree (every mode), then the mode's phases.  The parameters serve the modes in
+// turn: `space` as result_of() says; `mask` is the path-hash mask (K0) or the GPUDIFF_UPSERT_* mode word (K10);
+// space_cap, used, slots and links are K0's alone; docs[i]'s spare words are K10's body offset or K13's kind
+// (tokenize.h tokdoc_*).
+template <int MINW, int MODE = kModeEncode>
+__global__ __launch_bounds__(256, MINW) void k_encode_docs(const TokDoc* __restrict__ docs, uint32_t n_docs,
+                                                     const uint8_t* __restrict__ json, uint8_t* __restrict__ scratch,
+                                                     uint8_t* __restrict__ space, uint64_t space_cap,
+                                                     unsigned long long* __restrict__ used, uint64_t mask,
+                                                     TokOut* __restrict__ out, const DSlot* __restrict__ slots,
+                                                     const DocLink* __restrict__ links) {
+    // per wave, one LDS area reused phase by phase (tokdev.h: the LDS map)
+    __shared__ __attribute__((aligned(16))) uint8_t s_lds[kWavesPerBlock][kLdsPerWave];
+
+    const uint32_t lane = lane_id();
+    const uint32_t wib = threadIdx.x >> 6;
+    const uint32_t doc_i = __builtin_amdgcn_readfirstlane(blockIdx.x * kWavesPerBlock + wib);
+    if (doc_i >= n_docs) return;
+    uint8_t* lds = s_lds[wib];
+    auto* const res = result_of<MODE>(space, out, doc_i);
+
+    const TokDoc D = docs[doc_i];
+    if (D.json_len > kTokMaxLen) {
+        if (lane == 0) write_status(res, GPUDIFF_TOK_SIZE);
+        return;
+    }
+    uint8_t* const work = scratch + D.scratch_off;
+    DocTree T;
+    T.d = json + D.json_off;
+    T.len = D.json_len;
+    T.lane = lane;
+    T.S = bind_scratch<MODE>(work, T.len);
+    T.ncap = node_cap(T.len);
+
+    PhaseClock mark{g_k0_prof, g_k0_prof_on != 0, lane, 0};
+    if (mark.on) mark.t_prev = wall_clock64();
+    scan_tokens(T, lds);
+    mark(PS_SCAN);
+    build_tree<MODE>(T, lds);
+
+    if constexpr (MODE == kModeMarshal) {
+        marshal_doc(T, work, (uint32_t)mask, space, tokdoc_marshal_off(D), res, lds, mark);
+    } else if constexpr (MODE == kModeRollup) {
+        rollup_doc(T, res, mark);
+    } else if constexpr (MODE == kModeNegotiate) {
+        negotiate_doc(T, tokdoc_neg_kind(D), res, lds, mark);
+    } else {
+        const uint64_t seed = slots ? ((slots[links[doc_i].slot].flags >> 8) & 0xFFu) : D.seed;
+        mark(PS_TREE);
+        uint32_t status = T.status;
+        const Regions G = bind_regions(T);
+        const LeafPlan P = encode_values(T, G, lds, status);
+        mark(PE_VALUES);
+        hash_paths(T, P, lds, seed, status);
+        mark(PE_HASHES);
+        const SortOrder O = sort_keys(T, P, lds, seed, mask, status);
+        mark(PE_SORT);
+        TokOut o{};
+        write_blob(T, G, P, O, seed, mask, space, space_cap, used, o, status);
+#if defined(K0_PROBE_VALU) || defined(K0_PROBE_SALU)
+        probe_instructions(lane, status, T.nn, o);
+#endif
+        o.status = status;
+        if (lane == 0) *res = o;
+        mark(PE_BLOB);
+    }
+}
+
 
 hipError_t k0_profile(int enable, uint64_t* out8) {
     if (out8) {

@@ -379,8 +379,7 @@ int gpudiff_wbatch_create(gpudiff_ctx* c, const uint8_t* const* docs, const size
         t.json_off = jb;
         t.json_len = l;
         t.scratch_off = sb;
-        t.pad[0] = (uint32_t)ob;
-        t.pad[1] = (uint32_t)(ob >> 32);
+        tokdoc_set_marshal_off(t, ob);
         if (l <= kTokMaxLen) {
             jb = (jb + l + kTokSlack + 15) & ~15ull;
             sb += marshal_scratch_bytes(l);
@@ -593,8 +592,7 @@ int gpudiff_write_plan_get_ex(gpudiff_ctx* c, gpudiff_ticket ticket, uint32_t mo
         TokDoc t = sp.hdocs[di];
         t.seed = 0;
         t.scratch_off = sb;
-        t.pad[0] = (uint32_t)ob;
-        t.pad[1] = (uint32_t)(ob >> 32);
+        tokdoc_set_marshal_off(t, ob);
         sb += marshal_scratch_bytes(t.json_len);
         ob += marshal_out_cap(t.json_len);
         wdoc[w] = (uint32_t)docs.size();

@@ -144,3 +144,21 @@ def test_build_id_hashes_contents_not_mtimes(tmp_path):
     f = tmp_path / "include" / "gpudiff_format.h"
     f.write_bytes(f.read_bytes() + b" ")
     assert buildinfo.source_id(str(tmp_path)) != a
+
+
+def test_build_id_inputs_are_the_sources():
+    """The lists the build ID and the object stamps hash (buildinfo.py) are what the sources are built from: every
+    file a quoted #include in kcp_amd/csrc names is listed, every listed header is included somewhere, and every
+    file in csrc is in one of the lists.  (A header missing from HEADERS escapes the build ID and the stamps.)"""
+    from kcp_amd import buildinfo as B
+    files = sorted(os.listdir(B.CSRC))
+    included = set()
+    for f in files:
+        text = open(os.path.join(B.CSRC, f), encoding="utf-8").read()
+        included |= {os.path.basename(p) for p in re.findall(r'^[ \t]*#[ \t]*include[ \t]*"([^"]+)"', text, flags=re.M)}
+    headers = set(B.HEADERS) | set(B.INCLUDE_NAMES)
+    assert included - headers == set()
+    assert headers - included == set()
+    listed = set(B.SOURCES) | set(B.SYNTH_SOURCES) | set(B.HEADERS) | set(B.MAPS)
+    assert set(files) == listed
+    assert len(B.HEADERS) == len(set(B.HEADERS)) and not set(B.HEADERS) & set(B.INCLUDE_NAMES)
