@@ -16,14 +16,22 @@
 // conversion, an escaped key, a duplicate key or a collision, ...) is
 // deferred: its row is conservative in the device pass, the slot is marked
 // pending, and gpudiff_wait re-does those events on the host with the
-// Go-exact encoder (the same decisions store.cpp makes), places the blobs,
-// diffs them and patches the results -- so every result equals the host
-// store's, and later batches defer events of pending slots until then.
+// Go-exact encoder (PairEncoder::store_decide, the one ladder store.cpp takes
+// its decisions from too), places the blobs, diffs them and patches the
+// results -- so every result equals the host store's, and later batches defer
+// events of pending slots until then.
+//
+// dstore_submit drives these phases, in order: refuse_if_strings_need_compaction, claim_ring_slot,
+// build_tables_pairs | build_tables_store, plan_upload (dstore_plan.h), grow_batch_buffers, stage_and_encode,
+// link_and_diff; the ticket's finisher is finish_batch.  resolve (from finish_batch, when K0 deferred events):
+// encode_deferred_pair | encode_deferred_store per event, slot_updates, place_conservative | place_and_diff,
+// merge_results.
 //
 // Contract of this mode: event buffers stay valid until gpudiff_wait on the
 // ticket returns (deferred events are re-read), and batches are waited in
 // submit order, at most two in flight.
 #include "dstore.h"
+#include "dstore_plan.h"
 #include "pathstr.h"
 
 #include <emmintrin.h>
@@ -39,26 +47,9 @@
 #include <unordered_map>
 #include <vector>
 
-#include "tokenize.h"
-
 using namespace gd;
 
 namespace {
-
-constexpr uint64_t kScratchCap = 2ull << 30;  // K0 working area, reused across launches
-// a device-encoded batch's JSON is staged, uploaded and encoded in up to kMaxUpChunks chunks of at least
-// kUpChunkBytes (whole documents): the smaller the chunks, the sooner the first upload starts and the shorter
-// the last chunk's K0 after the copy stream is done.  GPUDIFF_H2D_CHUNK_MIB / GPUDIFF_H2D_MAX_CHUNKS (read once
-// per store, A/B tuning only) override them; round 3 used 4 chunks of >= 16 MiB.
-constexpr uint32_t kMaxUpChunks = 16;
-constexpr uint64_t kUpChunkBytes = 16ull << 20;
-// ... and of at least kMinChunkDocs documents: each chunk's K0 launch (a wave per document) should fill the
-// chip's ~8k resident waves twice over (r04m: 12 chunks of 5.4k documents made config5's K0 6.4 ms, from 4.1)
-constexpr uint64_t kMinChunkDocs = 16384;
-// store mode: the K0 stage on the kernel stream.  The decoupled form (K0 stage on its own stream; compaction,
-// Delete and the host resolution's placement ordered against it) measured within box noise on config 5
-// (profiles/r04zs) and stays compiled out until a measurement shows a gain
-constexpr bool kDecoupleStore = false;
 
 struct Ring {
     gpudiff_dbatch* d = nullptr;  // rows, pair_ids, results; pool = the store's current space
@@ -149,12 +140,6 @@ struct DStore {
     // previous diff pass (its space) -- so a batch's K0 overlaps the previous batch's diff pass on the kernel stream
     hipStream_t ks0 = nullptr;
     int last_ring = -1;  // the ring slot of the previous submit
-    // store mode with kDecoupleStore (off): the K0 stage on ks0 there too; whatever the kernel stream
-    // does to the slot table or the space between submits (compaction, Delete, the host resolution's placement)
-    // first waits for the last K0 stage and sets st_slot_ops, and the next K0 stage then waits for the kernel stream
-    bool dec_store = false;
-    bool st_slot_ops = false;
-    hipEvent_t st_ev = nullptr;
     uint64_t* sizes = nullptr;
     uint64_t* tile_sums = nullptr;
     uint8_t* scratch = nullptr;
@@ -233,16 +218,6 @@ int grow_dev(T** p, uint64_t* cap, uint64_t need) {
     return GPUDIFF_OK;
 }
 
-// a kernel-stream operation on the slot table or the space (store mode with the K0 stage on its own stream):
-// after the last K0 stage, and the next K0 stage waits for it
-int before_st_slot_op(DStore* s) {
-    if (!s->dec_store) return GPUDIFF_OK;
-    if (s->last_ring >= 0 && s->ring[s->last_ring].k0_recorded)
-        HIPCHK(hipStreamWaitEvent(s->c->stream, s->ring[s->last_ring].k0_done, 0));
-    s->st_slot_ops = true;
-    return GPUDIFF_OK;
-}
-
 // packs the live blobs into the other space (stream-ordered), then reads the
 // exact append point back
 int compact(DStore* s) {
@@ -251,7 +226,6 @@ int compact(DStore* s) {
     // that space would overwrite its superseded blobs first (dstore_submit refuses such a submit before it gets here)
     for (const Ring& R : s->ring)
         if (R.outstanding && R.strs && R.space_idx == 1 - s->cur) return GPUDIFF_E_STATE;
-    if (int rc = before_st_slot_op(s)) return rc;
     HIPCHK(launch_compact_store(c->stream, s->slots, s->max_slots, s->space[s->cur], s->space[1 - s->cur], s->sizes,
                                 s->tile_sums, s->used_dev));
     s->cur = 1 - s->cur;
@@ -396,357 +370,259 @@ void host_path(const HostPaths& hp, const ResultStore& r, uint32_t q, uint64_t m
 }
 
 // ------------------------------------------------------------------ host resolution
+// a slot as the resolution sees it: the device's entry as fetched, then as the batch's deferred events leave it
+// (d.off: absolute, or kRelTag | offset in the resolution pool), and its path table once a decision has read it
 struct HostSlot {
-    bool fetched = false;
-    bool live = false, has_status = false;
-    uint32_t seed = 0;
-    uint64_t off = 0;  // absolute, or kRelTag | offset in the resolution pool
-    uint32_t sl = 0, sar = 0, tl = 0, tar = 0, bytes = 0, n_tab = 0;
+    DStore* s = nullptr;  // set once fetched
+    DSlot d{};
     bool tab_loaded = false;
     PathTable tab;
+    bool live() const { return d.flags & DS_LIVE; }
+    uint32_t seed() const { return (d.flags >> 8) & 0xFF; }
+    void empty() {
+        d.flags &= ~DS_LIVE;
+        tab_loaded = false;
+    }
 };
 
 int fetch_slot(DStore* s, uint32_t slot, HostSlot& H) {
-    DSlot d;
-    HIPCHK(hipMemcpy(&d, s->slots + slot, sizeof(DSlot), hipMemcpyDeviceToHost));
-    H.fetched = true;
-    H.live = d.flags & DS_LIVE;
-    H.has_status = d.flags & DS_HAS_STATUS;
-    H.seed = (d.flags >> 8) & 0xFF;
-    H.off = d.off;
-    H.sl = d.spec_l;
-    H.sar = d.spec_ar;
-    H.tl = d.stat_l;
-    H.tar = d.stat_ar;
-    H.bytes = d.bytes;
-    H.n_tab = d.n_tab;
+    HIPCHK(hipMemcpy(&H.d, s->slots + slot, sizeof(DSlot), hipMemcpyDeviceToHost));
+    H.s = s;
     H.tab_loaded = false;
     return GPUDIFF_OK;
 }
 
-// the path table of a device-resident blob: its trailer
-int load_tab(DStore* s, HostSlot& H) {
+// the path table of a device-resident blob, its trailer, fetched when store_decide first reads it (ResidentTabFn)
+int load_tab(void* slot, const PathTable** out) {
+    HostSlot& H = *(HostSlot*)slot;
+    *out = &H.tab;
     if (H.tab_loaded) return GPUDIFF_OK;
-    const uint64_t segs = gpudiff_blob_body(H.sl, H.sar, H.tl, H.tar);  // the table follows the body
-    H.tab.n = H.n_tab;
-    H.tab.data.resize(H.bytes - segs);
+    const uint64_t segs = gpudiff_blob_body(H.d.spec_l, H.d.spec_ar, H.d.stat_l, H.d.stat_ar);  // the table follows
+    H.tab.n = H.d.n_tab;
+    H.tab.data.resize(H.d.bytes - segs);
     if (!H.tab.data.empty())
-        HIPCHK(hipMemcpy(H.tab.data.data(), s->space[s->cur] + H.off + segs, H.tab.data.size(), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(H.tab.data.data(), H.s->space[H.s->cur] + H.d.off + segs, H.tab.data.size(),
+                         hipMemcpyDeviceToHost));
     H.tab_loaded = true;
     return GPUDIFF_OK;
 }
 
-void set_tab(HostSlot& H, const FlatObject& o) {
-    H.tab = o.tab;
-    H.n_tab = o.tab.n;
-    H.tab_loaded = true;
-}
-
-// Re-does the batch's deferred events on the host (store.cpp's decisions),
-// diffs them on the device and patches rs.
-int resolve(DStore* s, Ring& R, ResultStore& rs) {
-    gpudiff_ctx* c = s->c;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (s->dec_store) {  // the slot reads below see every K0 stage submitted so far, and the placement follows them
-        HIPCHK(hipStreamSynchronize(s->ks0));
-        s->st_slot_ops = true;
-    }
-    std::vector<uint8_t> def(R.nev);
-    if (R.nev) HIPCHK(hipMemcpy(def.data(), R.ddef, R.nev, hipMemcpyDeviceToHost));
-    std::vector<uint32_t> drows;
-    for (uint32_t i = 0; i < R.nev; i++)
-        if (def[i]) drows.push_back(i);
-    if (drows.empty()) return GPUDIFF_OK;
-    s->deferred_total += drows.size();
-    int rc;
-    PairEncoder& enc = *s->enc;
-    Arena arena_new, arena_old;
-    FlatObject fn, fo;
-    std::vector<uint8_t> pool;
-    std::vector<gpudiff_pair_row> rows(drows.size());
+// The working set of one batch's host resolution: its deferred events, their re-encoded blobs and rows, and the
+// slots they touch.
+struct Deferred {
+    std::vector<uint8_t> def;     // per event of the batch: K0 deferred it
+    std::vector<uint32_t> drows;  // the deferred events, ascending
+    std::vector<uint8_t> pool;    // their blobs, placed behind the append point
+    std::vector<gpudiff_pair_row> rows;  // [drows.size()]
     // GPUDIFF_OPT_PATH_STRINGS: these events' strings come from the objects flattened here (their blobs carry no
     // table in pair mode, the re-encoded old side none in store mode)
-    const bool strs = rs.ps.on;
-    std::vector<HostPaths> hp(strs ? drows.size() : 0);
+    bool strs = false;
+    std::vector<HostPaths> hp;  // [drows.size()], or empty
     std::unordered_map<uint32_t, HostSlot> hs;
-    std::vector<uint32_t> touched;
-    for (size_t k = 0; k < drows.size(); k++) {
-        const gpudiff_event& e = R.events[drows[k]];
-        if (s->pair_mode) {  // gpudiff_encode_pairs' decisions on (old_json, new_json)
-            gpudiff_pair_row& r = rows[k];
-            memset(&r, 0, sizeof(r));
-            r.pair_id = e.pair_id;
-            r.cluster_id = e.cluster_id;
-            uint32_t seed = 0;
-            if (e.old_json && enc.flatten_json(e.old_json, e.old_len, arena_old, fo) &&
-                enc.flatten_json(e.new_json, e.new_len, arena_new, fn) && enc.pair_seed(fo, fn, &seed)) {
-                uint64_t oa, ob;
-                enc.write_object(fo, pool, &oa, &r.spec_l_a, &r.spec_ar_a, &r.stat_l_a, &r.stat_ar_a);
-                enc.write_object(fn, pool, &ob, &r.spec_l_b, &r.spec_ar_b, &r.stat_l_b, &r.stat_ar_b);
-                r.off_a = kRelTag | oa;
-                r.off_b = kRelTag | ob;
-                r.flags_a = (fo.flags & GPUDIFF_OBJ_HAS_STATUS) | (seed << GPUDIFF_OBJ_SEED_SHIFT);
-                r.flags_b = (fn.flags & GPUDIFF_OBJ_HAS_STATUS) | (seed << GPUDIFF_OBJ_SEED_SHIFT);
-                if (strs) {
-                    hp[k].a.of_flat(fo);
-                    hp[k].b.of_flat(fn);
-                }
-            } else {
-                r.flags_a = r.flags_b = GPUDIFF_OBJ_DECODE_ERR;
-            }
-            continue;
-        }
-        HostSlot& S = hs[e.slot];
-        if (!S.fetched) {
-            if ((rc = fetch_slot(s, e.slot, S))) return rc;
-            touched.push_back(e.slot);
-        }
-        gpudiff_pair_row& r = rows[k];
-        memset(&r, 0, sizeof(r));
-        r.pair_id = e.pair_id;
-        r.cluster_id = e.cluster_id;
-        auto conservative = [&]() { r.flags_a = r.flags_b = GPUDIFF_OBJ_DECODE_ERR; };
-        if (!enc.flatten_json(e.new_json, e.new_len, arena_new, fn)) {
-            conservative();
-            S.live = false;
-            S.tab_loaded = false;
-            continue;
-        }
-        bool ok = false, pair_error = false, a_live = false;
-        uint32_t seed = 0;
-        uint64_t a_off = 0;
-        uint32_t a_sl = 0, a_sar = 0, a_tl = 0, a_tar = 0, a_of = 0;
-        auto a_is_slot = [&]() {
-            a_live = true;
-            // the slot's blob as it is when k_place runs (a compaction may move it)
-            a_off = (S.off & kRelTag) ? S.off : (kSlotTag | e.slot);
-            a_sl = S.sl;
-            a_sar = S.sar;
-            a_tl = S.tl;
-            a_tar = S.tar;
-            a_of = S.has_status ? GPUDIFF_OBJ_HAS_STATUS : 0u;
-            if (strs) hp[k].a.of_table(S.tab, S.seed);  // the table load_tab fetched (or the previous event's)
-        };
-        if (S.live && S.seed == 0) {
-            if ((rc = load_tab(s, S))) return rc;
-            if (enc.hash_single(fn, 0) && tab_agree(tab_view(S.tab), tab_view(fn.tab))) {
-                ok = true;
-                a_is_slot();
-            }
-        }
-        if (!ok && e.old_json) {
-            if (enc.flatten_json(e.old_json, e.old_len, arena_old, fo) && enc.pair_seed(fo, fn, &seed)) {
-                uint64_t off;
-                enc.write_object(fo, pool, &off, &a_sl, &a_sar, &a_tl, &a_tar);
-                a_live = true;
-                a_off = kRelTag | off;
-                a_of = fo.flags & GPUDIFF_OBJ_HAS_STATUS;
-                if (strs) hp[k].a.of_flat(fo);
-                s->st.old_encoded++;
-                if (S.live) s->st.reseeded++;
-                ok = true;
-            } else {
-                pair_error = true;
-            }
-        } else if (!ok && S.live && S.seed) {
-            if ((rc = load_tab(s, S))) return rc;
-            if (enc.hash_single(fn, S.seed) && tab_agree(tab_view(S.tab), tab_view(fn.tab))) {
-                ok = true;
-                seed = S.seed;
-                a_is_slot();
-            } else {
-                pair_error = true;
-                s->st.collisions_unresolved++;
-            }
-        } else if (!ok && !S.live) {
-            ok = enc.first_seed(fn, &seed);
-            pair_error = !ok;
-        } else if (!ok) {
-            pair_error = true;
-            s->st.collisions_unresolved++;
-        }
-        if (pair_error) {
-            conservative();
-            if (!enc.store_seed(fn, &seed)) {
-                S.live = false;
-                S.tab_loaded = false;
-                continue;
-            }
-        }
-        uint64_t off;
-        uint32_t sl, sar, tl, tar, bytes;
-        enc.write_object_tab(fn, pool, &off, &sl, &sar, &tl, &tar, &bytes);
-        if (strs && !pair_error) hp[k].b.of_flat(fn);
-        if (!pair_error) {
-            r.off_a = a_live ? a_off : 0;
-            r.spec_l_a = a_sl;
-            r.spec_ar_a = a_sar;
-            r.stat_l_a = a_tl;
-            r.stat_ar_a = a_tar;
-            r.flags_a = a_of | (seed << GPUDIFF_OBJ_SEED_SHIFT);
-            r.off_b = kRelTag | off;
-            r.spec_l_b = sl;
-            r.spec_ar_b = sar;
-            r.stat_l_b = tl;
-            r.stat_ar_b = tar;
-            r.flags_b = (fn.flags & GPUDIFF_OBJ_HAS_STATUS) | (seed << GPUDIFF_OBJ_SEED_SHIFT);
-        }
-        S.live = true;
-        S.seed = seed;
-        S.has_status = fn.flags & GPUDIFF_OBJ_HAS_STATUS;
-        S.off = kRelTag | off;
-        S.sl = sl;
-        S.sar = sar;
-        S.tl = tl;
-        S.tar = tar;
-        S.bytes = bytes;
-        set_tab(S, fn);
+    std::vector<uint32_t> touched;  // hs's slots in first-touch order
+    Arena arena_new, arena_old;
+    FlatObject fn, fo;
+};
+
+gpudiff_pair_row& deferred_row(Deferred& W, size_t k, const gpudiff_event& e) {
+    gpudiff_pair_row& r = W.rows[k];
+    memset(&r, 0, sizeof(r));
+    r.pair_id = e.pair_id;
+    r.cluster_id = e.cluster_id;
+    return r;
+}
+
+// pair mode: gpudiff_encode_pairs' decisions on (old_json, new_json)
+void encode_deferred_pair(PairEncoder& enc, const gpudiff_event& e, Deferred& W, size_t k) {
+    gpudiff_pair_row& r = deferred_row(W, k, e);
+    uint32_t seed = 0;
+    if (!(e.old_json && enc.flatten_json(e.old_json, e.old_len, W.arena_old, W.fo) &&
+          enc.flatten_json(e.new_json, e.new_len, W.arena_new, W.fn) && enc.pair_seed(W.fo, W.fn, &seed))) {
+        r.flags_a = r.flags_b = GPUDIFF_OBJ_DECODE_ERR;
+        return;
     }
-    // slot states (forgotten-since slots keep their forget)
+    uint64_t oa, ob;
+    enc.write_object(W.fo, W.pool, &oa, &r.spec_l_a, &r.spec_ar_a, &r.stat_l_a, &r.stat_ar_a);
+    enc.write_object(W.fn, W.pool, &ob, &r.spec_l_b, &r.spec_ar_b, &r.stat_l_b, &r.stat_ar_b);
+    r.off_a = kRelTag | oa;
+    r.off_b = kRelTag | ob;
+    r.flags_a = (W.fo.flags & GPUDIFF_OBJ_HAS_STATUS) | (seed << GPUDIFF_OBJ_SEED_SHIFT);
+    r.flags_b = (W.fn.flags & GPUDIFF_OBJ_HAS_STATUS) | (seed << GPUDIFF_OBJ_SEED_SHIFT);
+    if (W.strs) {
+        W.hp[k].a.of_flat(W.fo);
+        W.hp[k].b.of_flat(W.fn);
+    }
+}
+
+// store mode: the host store's decision for the event (store_decide), its blobs into W.pool with offsets relative
+// to the placement, and the slot's state after it
+int encode_deferred_store(DStore* s, const gpudiff_event& e, Deferred& W, size_t k) {
+    PairEncoder& enc = *s->enc;
+    HostSlot& S = W.hs[e.slot];
+    if (!S.s) {
+        if (int rc = fetch_slot(s, e.slot, S)) return rc;
+        W.touched.push_back(e.slot);
+    }
+    gpudiff_pair_row& r = deferred_row(W, k, e);
+    const StoreDecision D = enc.store_decide(S.live(), S.seed(), load_tab, &S, e.old_json, e.old_len, e.new_json,
+                                             e.new_len, W.arena_old, W.arena_new, W.fo, W.fn);
+    if (D.rc) return D.rc;
+    s->st.old_encoded += D.old_encoded;
+    s->st.reseeded += D.reseeded;
+    s->st.collisions_unresolved += D.unresolved;
+    const bool pair_error = D.rung == StoreRung::kPairError;
+    if (pair_error) r.flags_a = r.flags_b = GPUDIFF_OBJ_DECODE_ERR;  // conservative
+    if (!D.store_ok) {
+        S.empty();
+        return GPUDIFF_OK;
+    }
+    if (D.rung == StoreRung::kResidentSeed0 || D.rung == StoreRung::kResidentSlotSeed) {
+        // the slot's blob as it is when k_place runs (a compaction may move it)
+        r.off_a = (S.d.off & kRelTag) ? S.d.off : (kSlotTag | e.slot);
+        r.spec_l_a = S.d.spec_l;
+        r.spec_ar_a = S.d.spec_ar;
+        r.stat_l_a = S.d.stat_l;
+        r.stat_ar_a = S.d.stat_ar;
+        r.flags_a = ((S.d.flags & DS_HAS_STATUS) ? GPUDIFF_OBJ_HAS_STATUS : 0u) | (D.seed << GPUDIFF_OBJ_SEED_SHIFT);
+        if (W.strs) W.hp[k].a.of_table(S.tab, S.seed());  // the table load_tab fetched (or the previous event's)
+    } else if (D.rung == StoreRung::kReencodedOld) {
+        uint64_t off;
+        enc.write_object(W.fo, W.pool, &off, &r.spec_l_a, &r.spec_ar_a, &r.stat_l_a, &r.stat_ar_a);
+        r.off_a = kRelTag | off;
+        r.flags_a = (W.fo.flags & GPUDIFF_OBJ_HAS_STATUS) | (D.seed << GPUDIFF_OBJ_SEED_SHIFT);
+        if (W.strs) W.hp[k].a.of_flat(W.fo);
+    } else if (!pair_error) {  // first sighting: no old side
+        r.flags_a = D.seed << GPUDIFF_OBJ_SEED_SHIFT;
+    }
+    uint64_t off;
+    uint32_t sl, sar, tl, tar, bytes;
+    enc.write_object_tab(W.fn, W.pool, &off, &sl, &sar, &tl, &tar, &bytes);
+    if (!pair_error) {
+        if (W.strs) W.hp[k].b.of_flat(W.fn);
+        r.off_b = kRelTag | off;
+        r.spec_l_b = sl;
+        r.spec_ar_b = sar;
+        r.stat_l_b = tl;
+        r.stat_ar_b = tar;
+        r.flags_b = (W.fn.flags & GPUDIFF_OBJ_HAS_STATUS) | (D.seed << GPUDIFF_OBJ_SEED_SHIFT);
+    }
+    const uint32_t has_status = (W.fn.flags & GPUDIFF_OBJ_HAS_STATUS) ? DS_HAS_STATUS : 0u;
+    S.d = DSlot{kRelTag | off, sl, sar, tl, tar, bytes, DS_LIVE | has_status | (D.seed << 8), 0, W.fn.tab.n};
+    S.tab = W.fn.tab;
+    S.tab_loaded = true;
+    return GPUDIFF_OK;
+}
+
+// the touched slots' states for k_place (forgotten-since slots keep their forget)
+std::vector<SlotUpdate> slot_updates(DStore* s, const Ring& R, const Deferred& W) {
     std::vector<SlotUpdate> ups;
-    for (uint32_t slot : touched) {
+    for (uint32_t slot : W.touched) {
         auto f = s->forgotten.find(slot);
         if (f != s->forgotten.end() && f->second >= R.batch) continue;
-        const HostSlot& S = hs[slot];
+        const HostSlot& S = W.hs.at(slot);
         SlotUpdate u{};
         u.slot = slot;
         u.batch = R.batch;
-        if (S.live) {
-            u.entry.off = S.off;
-            u.entry.spec_l = S.sl;
-            u.entry.spec_ar = S.sar;
-            u.entry.stat_l = S.tl;
-            u.entry.stat_ar = S.tar;
-            u.entry.bytes = S.bytes;
-            u.entry.n_tab = S.n_tab;
-            u.entry.flags = DS_LIVE | (S.has_status ? DS_HAS_STATUS : 0u) | (S.seed << 8);
-        } else {
-            s->seen[slot] = 0;  // the next event stages its old object again
-        }
+        if (S.live()) u.entry = S.d;  // as its last deferred event wrote it
+        else s->seen[slot] = 0;       // the next event stages its old object again
         ups.push_back(u);
     }
-    // place: blobs behind the append point, rows, slot states
-    const uint64_t pbytes = (pool.size() + GPUDIFF_BLOB_ALIGN - 1) & ~(uint64_t)(GPUDIFF_BLOB_ALIGN - 1);
-    pool.resize(pbytes, 0);
-    if ((rc = ensure_space(s, pbytes, pbytes))) {
-        if (rc != GPUDIFF_E_CAPACITY) return rc;
-        // The space cannot take the re-encoded blobs even after a compaction (K0 deferred these
-        // events for lack of space, and the host's blobs do not fit either).  The store stays
-        // usable: the events are reported dirty with GPUDIFF_DECODE_ERROR (the reference's
-        // conservative rule, specsyncer.go:20-22: never "equal") and their slots are emptied, so
-        // each slot's next event stages its old object again.
-        for (SlotUpdate& u : ups) {
-            memset(&u.entry, 0, sizeof(u.entry));
-            s->seen[u.slot] = 0;
-        }
-        if ((rc = grow_dev(&s->res_ups, &s->res_ups_cap, std::max<size_t>(ups.size(), 1)))) return rc;
-        if (!ups.empty()) HIPCHK(hipMemcpy(s->res_ups, ups.data(), ups.size() * sizeof(SlotUpdate), hipMemcpyHostToDevice));
-        HIPCHK(hipMemsetAsync(s->res_err, 0, 4, c->stream));
-        HIPCHK(launch_place(c->stream, nullptr, 0, s->space[s->cur], s->used_dev, s->space_bytes, nullptr, nullptr, 0,
-                            s->res_ups, (uint32_t)ups.size(), s->slots, s->ctr, s->res_err));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        s->st.space_conservative += drows.size();
-        ResultStore out;
-        out.flags.resize(R.nev);
-        out.off.push_back(0);
-        if (strs) {
-            out.ps.on = true;
-            out.ps.n_unresolved = rs.ps.n_unresolved;
-            out.ps.begin();
-        }
-        size_t jr = 0;
-        for (uint32_t i = 0; i < R.nev; i++) {
-            uint8_t f = rs.flags[i];
-            uint32_t lo = 0, hi = 0;
-            if (f & (GPUDIFF_SPEC_DIRTY | GPUDIFF_STATUS_DIRTY)) {
-                lo = rs.off[jr];
-                hi = rs.off[jr + 1];
-                jr++;
-            }
-            if (def[i]) {
-                f = GPUDIFF_SPEC_DIRTY | GPUDIFF_STATUS_DIRTY | GPUDIFF_DECODE_ERROR;
-                lo = hi = 0;
-            }
-            out.flags[i] = f;
-            const uint32_t pid = R.events[i].pair_id;
-            if (f & GPUDIFF_SPEC_DIRTY) out.spec.push_back(pid);
-            if (f & GPUDIFF_STATUS_DIRTY) out.status.push_back(pid);
-            if (f & (GPUDIFF_SPEC_DIRTY | GPUDIFF_STATUS_DIRTY)) {
-                out.dirty.push_back(pid);
-                for (uint32_t q = lo; q < hi; q++) {
-                    out.hashes.push_back(rs.hashes[q]);
-                    out.kinds.push_back(rs.kinds[q]);
-                    if (strs) out.ps.push(rs.ps.bytes() + rs.ps.offsets()[q], rs.ps.offsets()[q + 1] - rs.ps.offsets()[q]);
-                }
-                out.off.push_back((uint32_t)out.hashes.size());
-            }
-        }
-        if (strs) out.ps.finish();
-        rs = std::move(out);
-        return GPUDIFF_OK;
+    return ups;
+}
+
+// the slot states on the device, and k_place's error word cleared: what both placements start with
+int upload_slot_updates(DStore* s, const std::vector<SlotUpdate>& ups) {
+    if (int rc = grow_dev(&s->res_ups, &s->res_ups_cap, std::max<size_t>(ups.size(), 1))) return rc;
+    if (!ups.empty()) HIPCHK(hipMemcpy(s->res_ups, ups.data(), ups.size() * sizeof(SlotUpdate), hipMemcpyHostToDevice));
+    HIPCHK(hipMemsetAsync(s->res_err, 0, 4, s->c->stream));
+    return GPUDIFF_OK;
+}
+
+// The space cannot take the re-encoded blobs even after a compaction (K0 deferred these events for lack of space,
+// and the host's blobs do not fit either).  The store stays usable: the events are reported dirty with
+// GPUDIFF_DECODE_ERROR (the reference's conservative rule, specsyncer.go:20-22: never "equal") and their slots are
+// emptied, so each slot's next event stages its old object again.
+int place_conservative(DStore* s, std::vector<SlotUpdate>& ups, size_t n_deferred) {
+    for (SlotUpdate& u : ups) {
+        memset(&u.entry, 0, sizeof(u.entry));
+        s->seen[u.slot] = 0;
     }
+    if (int rc = upload_slot_updates(s, ups)) return rc;
+    HIPCHK(launch_place(s->c->stream, nullptr, 0, s->space[s->cur], s->used_dev, s->space_bytes, nullptr, nullptr, 0,
+                        s->res_ups, (uint32_t)ups.size(), s->slots, s->ctr, s->res_err));
+    HIPCHK(hipStreamSynchronize(s->c->stream));
+    s->st.space_conservative += n_deferred;
+    return GPUDIFF_OK;
+}
+
+// place: blobs behind the append point, rows, slot states; then the diff pass over the placed rows into r2
+int place_and_diff(DStore* s, const Deferred& W, const std::vector<SlotUpdate>& ups, ResultStore& r2) {
+    gpudiff_ctx* c = s->c;
+    const uint64_t pbytes = W.pool.size();
+    const size_t nr = W.rows.size();
+    int rc;
     if ((rc = grow_dev(&s->res_stage, &s->res_stage_cap, std::max<uint64_t>(pbytes, 16)))) return rc;
-    if ((rc = grow_dev(&s->res_ups, &s->res_ups_cap, std::max<size_t>(ups.size(), 1)))) return rc;
     gpudiff_dbatch* d = s->res_d;
-    if (d->max_pairs < rows.size()) {
+    if (d->max_pairs < nr) {
         gpudiff_dbatch_free(c, d);
         s->res_d = nullptr;
-        if ((rc = gpudiff_dbatch_create(c, 16, rows.size() + rows.size() / 2, &s->res_d))) return rc;
+        if ((rc = gpudiff_dbatch_create(c, 16, nr + nr / 2, &s->res_d))) return rc;
         d = s->res_d;
         (void)hipFree(d->pool);
         d->pool = nullptr;
         d->pool_borrowed = true;
     }
-    if (pbytes) HIPCHK(hipMemcpy(s->res_stage, pool.data(), pbytes, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d->rows, rows.data(), rows.size() * sizeof(gpudiff_pair_row), hipMemcpyHostToDevice));
-    if (!ups.empty()) HIPCHK(hipMemcpy(s->res_ups, ups.data(), ups.size() * sizeof(SlotUpdate), hipMemcpyHostToDevice));
-    HIPCHK(hipMemsetAsync(s->res_err, 0, 4, c->stream));
+    if (pbytes) HIPCHK(hipMemcpy(s->res_stage, W.pool.data(), pbytes, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d->rows, W.rows.data(), nr * sizeof(gpudiff_pair_row), hipMemcpyHostToDevice));
+    if ((rc = upload_slot_updates(s, ups))) return rc;
     HIPCHK(launch_place(c->stream, s->res_stage, pbytes, s->space[s->cur], s->used_dev, s->space_bytes, d->rows,
-                        d->pair_ids, (uint32_t)rows.size(), s->res_ups, (uint32_t)ups.size(), s->slots, s->ctr,
-                        s->res_err));
+                        d->pair_ids, (uint32_t)nr, s->res_ups, (uint32_t)ups.size(), s->slots, s->ctr, s->res_err));
     s->used_ub += pbytes;
     d->pool = s->space[s->cur];
     d->pool_cap = s->space_bytes;
-    d->n_pairs = rows.size();
+    d->n_pairs = nr;
     d->rows_gen++;
     gpudiff_ticket t2;
     if ((rc = gpudiff_diff(c, d, &t2))) return rc;
-    ResultStore r2;
     if ((rc = collect_results(c, d, r2))) return rc;
     c->tickets.erase(t2);
     d->ticket = 0;
     uint32_t err = 0;
     HIPCHK(hipMemcpy(&err, s->res_err, 4, hipMemcpyDeviceToHost));
-    if (err) return GPUDIFF_E_CAPACITY;
+    return err ? GPUDIFF_E_CAPACITY : GPUDIFF_OK;
+}
 
-    // patch: deferred rows take r2's results, the rest keep rs's
+// patch: deferred events take r2's results (r2 null, the conservative exit: each is dirty in both regions with
+// GPUDIFF_DECODE_ERROR and no paths), the rest keep rs's
+void merge_results(const Ring& R, const Deferred& W, ResultStore& rs, const ResultStore* r2, uint64_t mask) {
+    constexpr uint8_t kDirty = GPUDIFF_SPEC_DIRTY | GPUDIFF_STATUS_DIRTY;
     ResultStore out;
     out.flags.resize(R.nev);
     out.off.push_back(0);
-    if (strs) {
+    if (W.strs) {
         out.ps.on = true;
         out.ps.n_unresolved = rs.ps.n_unresolved;
         out.ps.begin();
     }
     size_t jr = 0, j2 = 0, k = 0;
     for (uint32_t i = 0; i < R.nev; i++) {
-        const bool d_in = (rs.flags[i] & (GPUDIFF_SPEC_DIRTY | GPUDIFF_STATUS_DIRTY)) != 0;
+        uint8_t f = rs.flags[i];
         uint32_t lo = 0, hi = 0;
         const ResultStore* src = &rs;
-        if (d_in) {
+        if (f & kDirty) {
             lo = rs.off[jr];
             hi = rs.off[jr + 1];
             jr++;
         }
-        uint8_t f = rs.flags[i];
         const size_t kd = k;  // the deferred event's index (rows, hp)
-        if (def[i]) {
-            f = r2.flags[k++];
-            src = &r2;
+        if (W.def[i]) {
+            k++;
             lo = hi = 0;
-            if (f & (GPUDIFF_SPEC_DIRTY | GPUDIFF_STATUS_DIRTY)) {
-                lo = r2.off[j2];
-                hi = r2.off[j2 + 1];
+            f = r2 ? r2->flags[kd] : (uint8_t)(kDirty | GPUDIFF_DECODE_ERROR);
+            if (r2 && (f & kDirty)) {
+                src = r2;
+                lo = r2->off[j2];
+                hi = r2->off[j2 + 1];
                 j2++;
             }
         }
@@ -754,20 +630,49 @@ int resolve(DStore* s, Ring& R, ResultStore& rs) {
         const uint32_t pid = R.events[i].pair_id;
         if (f & GPUDIFF_SPEC_DIRTY) out.spec.push_back(pid);
         if (f & GPUDIFF_STATUS_DIRTY) out.status.push_back(pid);
-        if (f & (GPUDIFF_SPEC_DIRTY | GPUDIFF_STATUS_DIRTY)) {
-            out.dirty.push_back(pid);
-            for (uint32_t q = lo; q < hi; q++) {
-                out.hashes.push_back(src->hashes[q]);
-                out.kinds.push_back(src->kinds[q]);
-                if (!strs) continue;
-                if (src == &r2) host_path(hp[kd], r2, q, c->hash_mask, out.ps);
-                else out.ps.push(rs.ps.bytes() + rs.ps.offsets()[q], rs.ps.offsets()[q + 1] - rs.ps.offsets()[q]);
-            }
-            out.off.push_back((uint32_t)out.hashes.size());
+        if (!(f & kDirty)) continue;
+        out.dirty.push_back(pid);
+        for (uint32_t q = lo; q < hi; q++) {
+            out.hashes.push_back(src->hashes[q]);
+            out.kinds.push_back(src->kinds[q]);
+            if (!W.strs) continue;
+            if (src == r2) host_path(W.hp[kd], *r2, q, mask, out.ps);
+            else out.ps.push(rs.ps.bytes() + rs.ps.offsets()[q], rs.ps.offsets()[q + 1] - rs.ps.offsets()[q]);
         }
+        out.off.push_back((uint32_t)out.hashes.size());
     }
-    if (strs) out.ps.finish();
+    if (W.strs) out.ps.finish();
     rs = std::move(out);
+}
+
+// Re-does the batch's deferred events on the host, diffs them on the device and patches rs.
+int resolve(DStore* s, Ring& R, ResultStore& rs) {
+    gpudiff_ctx* c = s->c;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    Deferred W;
+    W.def.resize(R.nev);
+    if (R.nev) HIPCHK(hipMemcpy(W.def.data(), R.ddef, R.nev, hipMemcpyDeviceToHost));
+    for (uint32_t i = 0; i < R.nev; i++)
+        if (W.def[i]) W.drows.push_back(i);
+    if (W.drows.empty()) return GPUDIFF_OK;
+    s->deferred_total += W.drows.size();
+    W.rows.resize(W.drows.size());
+    W.strs = rs.ps.on;
+    W.hp.resize(W.strs ? W.drows.size() : 0);
+    int rc;
+    for (size_t k = 0; k < W.drows.size(); k++) {
+        const gpudiff_event& e = R.events[W.drows[k]];
+        if (s->pair_mode) encode_deferred_pair(*s->enc, e, W, k);
+        else if ((rc = encode_deferred_store(s, e, W, k))) return rc;
+    }
+    std::vector<SlotUpdate> ups = slot_updates(s, R, W);
+    const uint64_t pbytes = (W.pool.size() + GPUDIFF_BLOB_ALIGN - 1) & ~(uint64_t)(GPUDIFF_BLOB_ALIGN - 1);
+    W.pool.resize(pbytes, 0);
+    ResultStore r2;
+    const bool fits = !(rc = ensure_space(s, pbytes, pbytes));
+    if (!fits && rc != GPUDIFF_E_CAPACITY) return rc;
+    if ((rc = fits ? place_and_diff(s, W, ups, r2) : place_conservative(s, ups, W.drows.size()))) return rc;
+    merge_results(R, W, rs, fits ? &r2 : nullptr, c->hash_mask);
     return GPUDIFF_OK;
 }
 
@@ -828,10 +733,6 @@ DStore* dstore_create(gpudiff_ctx* c, uint32_t max_slots, uint64_t space_bytes, 
         return fail(GPUDIFF_E_DEVICE);
     for (Ring& R : s->ring)
         if (hipEventCreateWithFlags(&R.pass_done, hipEventDisableTiming) != hipSuccess) return fail(GPUDIFF_E_DEVICE);
-    if (kDecoupleStore) {
-        if (hipEventCreateWithFlags(&s->st_ev, hipEventDisableTiming) != hipSuccess) return fail(GPUDIFF_E_DEVICE);
-        s->dec_store = true;
-    }
     if ((rc = gpudiff_dbatch_create(c, 16, 1024, &s->res_d))) return fail(rc);
     (void)hipFree(s->res_d->pool);
     s->res_d->pool = nullptr;
@@ -842,23 +743,57 @@ DStore* dstore_create(gpudiff_ctx* c, uint32_t max_slots, uint64_t space_bytes, 
     return s.release();
 }
 
-int dstore_submit(gpudiff_ctx* c, DStore* s, const gpudiff_event* ev, size_t n, gpudiff_ticket* ticket) {
-    if (s->broken) return GPUDIFF_E_STATE;
-    if (n > s->max_events) return GPUDIFF_E_INVAL;
-    if (!s->pair_mode && (c->flags & GPUDIFF_OPT_PATH_STRINGS)) {
-        // The batch in flight renders its paths, at its gpudiff_wait, from the space it was written to.  If a
-        // compaction has since left it behind in the other space, the next compaction packs into that space: a
-        // submit that may need one is refused before it changes anything (wait on the outstanding ticket first).
-        const Ring& O = s->ring[s->ring_next ^ 1u];
-        if (O.outstanding && O.strs && O.space_idx != s->cur) {
-            uint64_t pre = 0;  // >= the bound ensure_space is asked for below
-            for (size_t i = 0; i < n; i++)
-                pre += (5 * ((uint64_t)ev[i].new_len + (ev[i].old_json ? ev[i].old_len : 0))) / 2 + 768;
-            if (s->used_ub + pre > s->space_bytes) return GPUDIFF_E_STATE;
-        }
+// ------------------------------------------------------------------ submit
+namespace {
+
+// GPUDIFF_OPT_TIMING: the submit's host phases, t_sub[k] += the time since the previous lap
+struct Lap {
+    bool on;
+    double* t_sub;
+    std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
+    void operator()(int k) {
+        if (!on) return;
+        const auto now = std::chrono::steady_clock::now();
+        t_sub[k] += std::chrono::duration<double, std::milli>(now - t).count();
+        t = now;
     }
-    const auto t_host0 = std::chrono::steady_clock::now();
-    const bool timing = (c->flags & GPUDIFF_OPT_TIMING) != 0;
+};
+
+// The host-side description of one batch: the document table, the slot chains and their heads (in R.hmeta, laid
+// out for 2n documents), where each document's bytes are, and the sums the later phases size things by.
+struct BatchTables {
+    TokDoc* docs = nullptr;
+    DocLink* links = nullptr;
+    uint32_t* heads = nullptr;
+    uint64_t max_docs = 0, meta_bytes = 0;
+    std::vector<const uint8_t*> src;  // per document, the caller's bytes
+    uint32_t nd = 0, nh = 0;
+    uint64_t jbytes = 0;              // the staged JSON (build_tables adds the trailing kTokSlack last)
+    uint64_t bound = 0, floor = 0;    // the blobs' estimate that triggers compaction, and the least they take
+    uint64_t new_json_bytes = 0;
+    const uint8_t* zsrc = nullptr;    // zero copy: the caller's pinned buffer holds the staged layout (offset 0 here)
+    uint64_t links_off() const { return max_docs * sizeof(TokDoc); }
+    uint64_t heads_off() const { return max_docs * (sizeof(TokDoc) + sizeof(DocLink)); }
+};
+
+// GPUDIFF_OPT_PATH_STRINGS in store mode: the batch in flight renders its paths, at its gpudiff_wait, from the
+// space it was written to.  If a compaction has since left it behind in the other space, the next compaction packs
+// into that space: a submit that may need one is refused before it changes anything (wait on the outstanding
+// ticket first).
+bool refuse_if_strings_need_compaction(const DStore* s, const gpudiff_event* ev, size_t n) {
+    if (s->pair_mode || !(s->c->flags & GPUDIFF_OPT_PATH_STRINGS)) return false;
+    const Ring& O = s->ring[s->ring_next ^ 1u];
+    if (!(O.outstanding && O.strs && O.space_idx != s->cur)) return false;
+    uint64_t pre = 0;  // >= the bound ensure_space is asked for
+    for (size_t i = 0; i < n; i++)
+        pre += (5 * ((uint64_t)ev[i].new_len + (ev[i].old_json ? ev[i].old_len : 0))) / 2 + 768;
+    return s->used_ub + pre > s->space_bytes;
+}
+
+// The ring slot this submit takes, with its pinned buffers reusable.  dec: the K0 stage runs on its own streams
+// (it resets the space's append point there).
+int claim_ring_slot(DStore* s, bool dec, Ring** out) {
+    gpudiff_ctx* c = s->c;
     Ring& R = s->ring[s->ring_next];
     if (R.outstanding) {
         if (!s->pair_mode) return GPUDIFF_E_STATE;  // wait on the batch two submits back first
@@ -866,310 +801,231 @@ int dstore_submit(gpudiff_ctx* c, DStore* s, const gpudiff_event* ev, size_t n, 
         c->finishers.erase(R.ticket);
         R.outstanding = false;
     }
-    int rc;
     if (R.staged) HIPCHK(hipEventSynchronize(R.staged));
-    // pair mode with the K0 stage on its own streams (ks0 / ks): decoupled from the kernel stream
-    const bool dec = (s->pair_mode || s->dec_store) && s->ks0;
     if (s->pair_mode) {  // this ring slot's space, emptied behind its previous batch (stream order)
         s->cur = s->ring_next;
         s->used_dev = s->used_base + s->ring_next;
         s->used_ub = 0;
-        if (!dec) HIPCHK(hipMemsetAsync(s->used_dev, 0, 8, c->stream));  // (dec: on ks0, below)
+        if (!dec) HIPCHK(hipMemsetAsync(s->used_dev, 0, 8, c->stream));  // (dec: on ks0, in stage_and_encode)
     }
-    auto lap = [&, t = std::chrono::steady_clock::now()](int k) mutable {
-        if (!timing) return;
-        const auto now = std::chrono::steady_clock::now();
-        s->t_sub[k] += std::chrono::duration<double, std::milli>(now - t).count();
-        t = now;
-    };
-    lap(0);
-    const uint32_t batch = ++s->batch_seq;
+    *out = &R;
+    return GPUDIFF_OK;
+}
 
-    // 1. documents and slot chains
-    const uint64_t max_docs = 2 * (uint64_t)n;
-    const uint64_t meta_bytes = max_docs * (sizeof(TokDoc) + sizeof(DocLink)) + 4 * (uint64_t)n + 64;
-    if ((rc = grow_pinned(&R.hmeta, &R.hmeta_cap, meta_bytes))) return rc;
-    TokDoc* docs = (TokDoc*)R.hmeta;
-    DocLink* links = (DocLink*)(R.hmeta + max_docs * sizeof(TokDoc));
-    uint32_t* heads = (uint32_t*)(R.hmeta + max_docs * (sizeof(TokDoc) + sizeof(DocLink)));
-    std::vector<const uint8_t*> src;
-    src.reserve(max_docs);
-    const uint8_t* zsrc = nullptr;  // zero copy: the caller's pinned buffer holds the staged layout (offset 0 here)
-    uint32_t nd = 0, nh = 0;
-    uint64_t jbytes = 0, bound = 0, floor = 0, new_json_bytes = 0;
-    auto add_doc = [&](const uint8_t* p, size_t len, uint32_t slot, uint32_t row, const gpudiff_event& e) {
-        TokDoc& D = docs[nd];
-        memset(&D, 0, sizeof(D));
-        D.json_off = jbytes;
-        D.json_len = (uint32_t)len;
-        jbytes = (jbytes + len + kTokSlack + 15) & ~15ull;
-        // blob + path table: typically < 2.5x the JSON (the append estimate that triggers compaction);
-        // K0 defers a document that does not fit (SPACE) to the host
-        bound += (5 * (uint64_t)len) / 2 + 384;  // + the body's and the table's pads to 128 B
-        floor += len;
-        DocLink& L = links[nd];
-        memset(&L, 0, sizeof(L));
-        L.slot = slot;
-        L.row = row;
-        L.pair_id = e.pair_id;
-        L.cluster_id = e.cluster_id;
-        L.next = -1;
-        DStore::SlotState& ss = s->sstate[slot];
-        if (ss.stamp == batch) {
-            L.prev = ss.last;
-            links[L.prev].next = (int32_t)nd;
-        } else {
-            L.prev = -1;
-            ss.stamp = batch;
-            heads[nh++] = nd;
-        }
-        ss.last = (int32_t)nd;
-        src.push_back(p);
-        nd++;
-    };
-    if (s->pair_mode) {
-        // gpudiff_submit's pairs: event i is slot i with documents 2i (old) and 2i + 1 (new), so the tables
-        // are filled by the workers -- a per-thread byte sum, then each thread writes its range from its
-        // offset.  Same tables as add_doc builds (it is the order-dependent path for store events).
-        static const uint8_t kNone[1] = {0};
-        const uint32_t T = (uint32_t)std::min<size_t>(std::max(1u, c->threads), std::max<size_t>(1, n / 4096));
-        std::vector<uint64_t> part(4 * (size_t)T + 4, 0);  // per thread: JSON bytes, bound, floor, new bytes
-        std::atomic<int> bad{0};
-        src.resize(2 * n);
-        auto step = [](size_t len) -> uint64_t { return (len + kTokSlack + 15) & ~15ull; };
-        // Zero copy: every document in one gpudiff_host_alloc buffer, 16-B aligned, in pair order, each followed
-        // by its staged span (step) before the next -- then the buffer's range is the staged layout itself
-        uint8_t* zb = nullptr;
-        uint64_t zn = 0;
-        bool zc = ev[0].old_json && find_host_buf(c, ev[0].old_json, &zb, &zn);
-        std::atomic<int> zc_bad{0};
-        const uint8_t* zend = zb + zn - kTokSlack;  // the upload runs kTokSlack past the last document's span
-        workers(c).run(T, [&](uint32_t t) {
-            uint64_t jb = 0, bd = 0, fl = 0, nj = 0;
-            for (size_t i = n * t / T, i1 = n * (t + 1) / T; i < i1; i++) {
-                const gpudiff_event& e = ev[i];
-                if (e.slot != i || e.slot >= s->max_slots || !e.new_json || e.new_len > kTokMaxLen ||
-                    e.old_len > kTokMaxLen)
-                    bad.store(1, std::memory_order_relaxed);
-                if (zc) {
-                    const uint8_t* next = i + 1 < n ? ev[i + 1].old_json : zend;
-                    if (!e.old_json || e.old_json < zb || (((uintptr_t)e.old_json | (uintptr_t)e.new_json) & 15u) ||
-                        e.new_json < e.old_json + step(e.old_len) || !next || next < e.new_json + step(e.new_len) ||
-                        next > zend)
-                        zc_bad.store(1, std::memory_order_relaxed);
-                }
-                const size_t lo = e.old_json ? e.old_len : 0;
-                jb += step(lo) + step(e.new_len);
-                bd += (5 * (uint64_t)lo) / 2 + (5 * (uint64_t)e.new_len) / 2 + 768;
-                fl += lo + e.new_len;
-                nj += e.new_len;
+int map_tables(Ring& R, size_t n, BatchTables& B) {
+    B.max_docs = 2 * (uint64_t)n;
+    B.meta_bytes = B.max_docs * (sizeof(TokDoc) + sizeof(DocLink)) + 4 * (uint64_t)n + 64;
+    if (int rc = grow_pinned(&R.hmeta, &R.hmeta_cap, B.meta_bytes)) return rc;
+    B.docs = (TokDoc*)R.hmeta;
+    B.links = (DocLink*)(R.hmeta + B.links_off());
+    B.heads = (uint32_t*)(R.hmeta + B.heads_off());
+    B.src.reserve(B.max_docs);
+    return GPUDIFF_OK;
+}
+
+// gpudiff_submit's pairs: event i is slot i with documents 2i (old) and 2i + 1 (new), so the tables are filled by
+// the workers -- a per-thread byte sum, then each thread writes its range from its offset.  Same tables as
+// build_tables_store builds (that is the order-dependent path for store events).
+int build_tables_pairs(DStore* s, const gpudiff_event* ev, size_t n, uint32_t batch, BatchTables& B) {
+    gpudiff_ctx* c = s->c;
+    static const uint8_t kNone[1] = {0};  // an absent old object: decode error
+    const uint32_t T = (uint32_t)std::min<size_t>(std::max(1u, c->threads), std::max<size_t>(1, n / 4096));
+    std::vector<uint64_t> part(4 * (size_t)T + 4, 0);  // per thread: JSON bytes, bound, floor, new bytes
+    std::atomic<int> bad{0};
+    B.src.resize(2 * n);
+    // Zero copy: every document in one gpudiff_host_alloc buffer, 16-B aligned, in pair order, each followed
+    // by its staged span before the next -- then the buffer's range is the staged layout itself
+    uint8_t* zb = nullptr;
+    uint64_t zn = 0;
+    bool zc = ev[0].old_json && find_host_buf(c, ev[0].old_json, &zb, &zn);
+    std::atomic<int> zc_bad{0};
+    const uint8_t* zend = zb + zn - kTokSlack;  // the upload runs kTokSlack past the last document's span
+    const uint32_t max_slots = s->max_slots;
+    workers(c).run(T, [&part, &bad, &zc_bad, ev, n, T, zc, zb, zend, max_slots](uint32_t t) {
+        uint64_t jb = 0, bd = 0, fl = 0, nj = 0;
+        for (size_t i = n * t / T, i1 = n * (t + 1) / T; i < i1; i++) {
+            const gpudiff_event& e = ev[i];
+            if (e.slot != i || e.slot >= max_slots || !e.new_json || e.new_len > kTokMaxLen || e.old_len > kTokMaxLen)
+                bad.store(1, std::memory_order_relaxed);
+            if (zc) {
+                const uint8_t* next = i + 1 < n ? ev[i + 1].old_json : zend;
+                if (!e.old_json || e.old_json < zb || (((uintptr_t)e.old_json | (uintptr_t)e.new_json) & 15u) ||
+                    e.new_json < e.old_json + tok_staged_span(e.old_len) || !next ||
+                    next < e.new_json + tok_staged_span(e.new_len) || next > zend)
+                    zc_bad.store(1, std::memory_order_relaxed);
             }
-            uint64_t* q = &part[4 * (size_t)(t + 1)];
-            q[0] = jb, q[1] = bd, q[2] = fl, q[3] = nj;
-        });
-        if (bad.load()) return GPUDIFF_E_INVAL;
-        zc = zc && !zc_bad.load();
-        const uint8_t* zlo = ev[0].old_json;
-        for (uint32_t t = 1; t <= T; t++)
-            for (int k = 0; k < 4; k++) part[4 * (size_t)t + k] += part[4 * (size_t)(t - 1) + k];
-        workers(c).run(T, [&](uint32_t t) {
-            uint64_t off = part[4 * (size_t)t];
-            for (size_t i = n * t / T, i1 = n * (t + 1) / T; i < i1; i++) {
-                const gpudiff_event& e = ev[i];
-                const uint8_t* pj[2] = {e.old_json ? e.old_json : kNone, e.new_json};
-                const size_t len[2] = {e.old_json ? e.old_len : 0, e.new_len};
-                for (uint32_t h = 0; h < 2; h++) {
-                    const size_t k = 2 * i + h;
-                    TokDoc& D = docs[k];
-                    memset(&D, 0, sizeof(D));
-                    D.json_off = zc ? (uint64_t)(pj[h] - zlo) : off;
-                    D.json_len = (uint32_t)len[h];
-                    off += step(len[h]);
-                    if (zc)  // the staged span's padding, as the staging copy writes it (gpudiff.h: engine-owned)
-                        memset((uint8_t*)pj[h] + len[h], 0, step(len[h]) - len[h]);
-                    DocLink& L = links[k];
-                    memset(&L, 0, sizeof(L));
-                    L.slot = e.slot;
-                    L.row = h ? (uint32_t)i : kNoRow;
-                    L.pair_id = e.pair_id;
-                    L.cluster_id = e.cluster_id;
-                    L.prev = h ? (int32_t)(2 * i) : -1;
-                    L.next = h ? -1 : (int32_t)(2 * i + 1);
-                    src[k] = pj[h];
-                }
-                heads[i] = (uint32_t)(2 * i);
-                s->sstate[e.slot] = DStore::SlotState{batch, (int32_t)(2 * i + 1)};
-            }
-        });
-        const uint64_t* tot = &part[4 * (size_t)T];
-        nd = (uint32_t)(2 * n);
-        nh = (uint32_t)n;
-        jbytes = tot[0], bound = tot[1], floor = tot[2], new_json_bytes = tot[3];
-        if (zc) {
-            zsrc = zlo;
-            jbytes = (uint64_t)(ev[n - 1].new_json + step(ev[n - 1].new_len) - zlo);
-            s->st.zero_copy_batches++;
+            const size_t lo = e.old_json ? e.old_len : 0;
+            jb += tok_staged_span(lo) + tok_staged_span(e.new_len);
+            bd += (5 * (uint64_t)lo) / 2 + (5 * (uint64_t)e.new_len) / 2 + 768;
+            fl += lo + e.new_len;
+            nj += e.new_len;
         }
+        uint64_t* q = &part[4 * (size_t)(t + 1)];
+        q[0] = jb, q[1] = bd, q[2] = fl, q[3] = nj;
+    });
+    if (bad.load()) return GPUDIFF_E_INVAL;
+    zc = zc && !zc_bad.load();
+    const uint8_t* zlo = ev[0].old_json;
+    for (uint32_t t = 1; t <= T; t++)
+        for (int k = 0; k < 4; k++) part[4 * (size_t)t + k] += part[4 * (size_t)(t - 1) + k];
+    workers(c).run(T, [&part, &B, s, ev, n, T, zc, zlo, batch](uint32_t t) {
+        uint64_t off = part[4 * (size_t)t];
+        for (size_t i = n * t / T, i1 = n * (t + 1) / T; i < i1; i++) {
+            const gpudiff_event& e = ev[i];
+            const uint8_t* pj[2] = {e.old_json ? e.old_json : kNone, e.new_json};
+            const size_t len[2] = {e.old_json ? e.old_len : 0, e.new_len};
+            for (uint32_t h = 0; h < 2; h++) {
+                const size_t k = 2 * i + h;
+                TokDoc& D = B.docs[k];
+                memset(&D, 0, sizeof(D));
+                D.json_off = zc ? (uint64_t)(pj[h] - zlo) : off;
+                D.json_len = (uint32_t)len[h];
+                off += tok_staged_span(len[h]);
+                if (zc)  // the staged span's padding, as the staging copy writes it (gpudiff.h: engine-owned)
+                    memset((uint8_t*)pj[h] + len[h], 0, tok_staged_span(len[h]) - len[h]);
+                DocLink& L = B.links[k];
+                memset(&L, 0, sizeof(L));
+                L.slot = e.slot;
+                L.row = h ? (uint32_t)i : kNoRow;
+                L.pair_id = e.pair_id;
+                L.cluster_id = e.cluster_id;
+                L.prev = h ? (int32_t)(2 * i) : -1;
+                L.next = h ? -1 : (int32_t)(2 * i + 1);
+                B.src[k] = pj[h];
+            }
+            B.heads[i] = (uint32_t)(2 * i);
+            s->sstate[e.slot] = DStore::SlotState{batch, (int32_t)(2 * i + 1)};
+        }
+    });
+    const uint64_t* tot = &part[4 * (size_t)T];
+    B.nd = (uint32_t)(2 * n);
+    B.nh = (uint32_t)n;
+    B.jbytes = tot[0], B.bound = tot[1], B.floor = tot[2], B.new_json_bytes = tot[3];
+    if (zc) {
+        B.zsrc = zlo;
+        B.jbytes = (uint64_t)(ev[n - 1].new_json + tok_staged_span(ev[n - 1].new_len) - zlo);
+        s->st.zero_copy_batches++;
     }
-    for (size_t i = 0; i < n && !s->pair_mode; i++) {
+    B.jbytes += kTokSlack;
+    return GPUDIFF_OK;
+}
+
+// one staged document of a store batch, chained behind its slot's previous document of the batch
+void add_doc(DStore* s, BatchTables& B, uint32_t batch, const uint8_t* p, size_t len, uint32_t row,
+             const gpudiff_event& e) {
+    const uint32_t nd = B.nd++;
+    TokDoc& D = B.docs[nd];
+    memset(&D, 0, sizeof(D));
+    D.json_off = B.jbytes;
+    D.json_len = (uint32_t)len;
+    B.jbytes += tok_staged_span(len);
+    // blob + path table: typically < 2.5x the JSON (the append estimate that triggers compaction);
+    // K0 defers a document that does not fit (SPACE) to the host
+    B.bound += (5 * (uint64_t)len) / 2 + 384;  // + the body's and the table's pads to 128 B
+    B.floor += len;
+    DocLink& L = B.links[nd];
+    memset(&L, 0, sizeof(L));
+    L.slot = e.slot;
+    L.row = row;
+    L.pair_id = e.pair_id;
+    L.cluster_id = e.cluster_id;
+    L.next = -1;
+    DStore::SlotState& ss = s->sstate[e.slot];
+    if (ss.stamp == batch) {
+        L.prev = ss.last;
+        B.links[L.prev].next = (int32_t)nd;
+    } else {
+        L.prev = -1;
+        ss.stamp = batch;
+        B.heads[B.nh++] = nd;
+    }
+    ss.last = (int32_t)nd;
+    B.src.push_back(p);
+}
+
+// Store-mode zero copy: the documents this submit encodes -- per event, its old object on a slot's first sighting,
+// then its new one -- lie in one gpudiff_host_alloc buffer in that order, each 16-B aligned and followed by its
+// staged span, so the buffer's range is the staged layout (gaps between the documents, e.g. old objects the store
+// does not encode, are uploaded but never read).  No staging copy.
+void store_zero_copy(DStore* s, BatchTables& B) {
+    uint8_t* zb = nullptr;
+    uint64_t zn = 0;
+    if (!find_host_buf(s->c, B.src[0], &zb, &zn) || zn <= kTokSlack) return;
+    const uint8_t* zend = zb + zn - kTokSlack;  // the upload runs kTokSlack past the last document's span
+    const uint8_t* at = B.src[0];
+    for (uint32_t k = 0; k < B.nd; k++) {
+        const uint8_t* p = B.src[k];
+        if (!(p >= at && !((uintptr_t)p & 15u) && p + tok_staged_span(B.docs[k].json_len) <= zend)) return;
+        at = p + tok_staged_span(B.docs[k].json_len);
+    }
+    B.zsrc = B.src[0];
+    for (uint32_t k = 0; k < B.nd; k++) {
+        B.docs[k].json_off = (uint64_t)(B.src[k] - B.zsrc);
+        // the staged span's padding, as the staging copy writes it (gpudiff.h: engine-owned)
+        memset((uint8_t*)B.src[k] + B.docs[k].json_len, 0, tok_staged_span(B.docs[k].json_len) - B.docs[k].json_len);
+    }
+    B.jbytes = (uint64_t)(at - B.zsrc);
+    s->st.zero_copy_batches++;
+}
+
+// store events, in order: per event its new object, behind its old object on the slot's first sighting
+int build_tables_store(DStore* s, const gpudiff_event* ev, size_t n, uint32_t batch, BatchTables& B) {
+    for (size_t i = 0; i < n; i++) {
         const gpudiff_event& e = ev[i];
         if (i + 16 < n && ev[i + 16].slot < s->max_slots) {  // the slot state 16 events ahead
             __builtin_prefetch(&s->sstate[ev[i + 16].slot], 1);
-            if (!s->pair_mode) __builtin_prefetch(&s->seen[ev[i + 16].slot], 1);
+            __builtin_prefetch(&s->seen[ev[i + 16].slot], 1);
         }
         if (e.slot >= s->max_slots || !e.new_json || e.new_len > kTokMaxLen || e.old_len > kTokMaxLen)
             return GPUDIFF_E_INVAL;
-        if (s->pair_mode) {  // every pair: its old object, then its new one (an absent old object: decode error)
-            static const uint8_t kNone[1] = {0};
-            add_doc(e.old_json ? e.old_json : kNone, e.old_json ? e.old_len : 0, e.slot, kNoRow, e);
-        } else {
-            if (!s->seen[e.slot] && e.old_json) {  // first sighting: its old object is the old side
-                add_doc(e.old_json, e.old_len, e.slot, kNoRow, e);
-                s->st.old_encoded++;
-            }
-            s->seen[e.slot] = 1;
+        if (!s->seen[e.slot] && e.old_json) {  // first sighting: its old object is the old side
+            add_doc(s, B, batch, e.old_json, e.old_len, kNoRow, e);
+            s->st.old_encoded++;
         }
-        add_doc(e.new_json, e.new_len, e.slot, (uint32_t)i, e);
-        new_json_bytes += e.new_len;
+        s->seen[e.slot] = 1;
+        add_doc(s, B, batch, e.new_json, e.new_len, (uint32_t)i, e);
+        B.new_json_bytes += e.new_len;
     }
-    if (!s->pair_mode && nd) {
-        // Store-mode zero copy: the documents this submit encodes -- per event, its old object on a
-        // slot's first sighting, then its new one -- lie in one gpudiff_host_alloc buffer in that order, each 16-B
-        // aligned and followed by its staged span, so the buffer's range is the staged layout (gaps between the
-        // documents, e.g. old objects the store does not encode, are uploaded but never read).  No staging copy.
-        auto step = [](size_t len) -> uint64_t { return (len + kTokSlack + 15) & ~15ull; };
-        uint8_t* zb = nullptr;
-        uint64_t zn = 0;
-        if (find_host_buf(c, src[0], &zb, &zn) && zn > kTokSlack) {
-            const uint8_t* zend = zb + zn - kTokSlack;  // the upload runs kTokSlack past the last document's span
-            const uint8_t* at = src[0];
-            bool ok = true;
-            for (uint32_t k = 0; k < nd && ok; k++) {
-                const uint8_t* p = src[k];
-                ok = p >= at && !((uintptr_t)p & 15u) && p + step(docs[k].json_len) <= zend;
-                at = p + step(docs[k].json_len);
-            }
-            if (ok) {
-                zsrc = src[0];
-                for (uint32_t k = 0; k < nd; k++) {
-                    docs[k].json_off = (uint64_t)(src[k] - zsrc);
-                    // the staged span's padding, as the staging copy writes it (gpudiff.h: engine-owned)
-                    memset((uint8_t*)src[k] + docs[k].json_len, 0, step(docs[k].json_len) - docs[k].json_len);
-                }
-                jbytes = (uint64_t)(at - zsrc);
-                s->st.zero_copy_batches++;
-            }
-        }
-    }
-    jbytes += kTokSlack;
-    if (!zsrc && (rc = grow_pinned(&R.hjson, &R.hjson_cap, jbytes))) return rc;
-    const uint8_t* hsrc = zsrc ? zsrc : R.hjson;
-    lap(1);
-    // Chunks of the batch's JSON (by bytes, whole documents): the host copies chunk c into pinned
-    // staging while chunk c - 1 is uploading, and K0 starts on a chunk as soon as it has landed, so
-    // copy, upload and encode of one batch overlap instead of running back to back.
-    auto first_doc = [&](uint64_t b) -> uint32_t {  // first document starting at or after byte b
-        uint32_t lo = 0, hi = nd;
-        while (lo < hi) {
-            const uint32_t mid = (lo + hi) / 2;
-            if (docs[mid].json_off < b) lo = mid + 1;
-            else hi = mid;
-        }
-        return lo;
-    };
-    const uint32_t C = (uint32_t)std::min<uint64_t>(
-        std::min<uint64_t>(kMaxUpChunks, std::max<uint64_t>(1, nd / kMinChunkDocs)),
-        std::max<uint64_t>(1, jbytes / kUpChunkBytes));
-    uint32_t cdoc[kMaxUpChunks + 1];
-    for (uint32_t q = 0; q <= C; q++) cdoc[q] = q == C ? nd : first_doc(jbytes * q / C);
-    auto cbyte = [&](uint32_t q) -> uint64_t { return q == C || cdoc[q] >= nd ? jbytes : docs[cdoc[q]].json_off; };
-    // K0 scratch: per-document areas within launches of at most kScratchCap, never across a chunk
-    std::vector<std::pair<uint32_t, uint32_t>> launches;
-    std::vector<uint32_t> chunk_of_launch;
-    uint64_t max_sb = 0;  // the largest launch's scratch: one such area per K0 stream
-    for (uint32_t q = 0; q < C; q++) {
-        uint64_t sb = 0;
-        uint32_t first = cdoc[q];
-        for (uint32_t k = cdoc[q]; k < cdoc[q + 1]; k++) {
-            const uint64_t need = tok_scratch_bytes(docs[k].json_len);
-            if (sb && sb + need > std::max(kScratchCap, need)) {
-                launches.emplace_back(first, k);
-                chunk_of_launch.push_back(q);
-                first = k;
-                sb = 0;
-            }
-            docs[k].scratch_off = sb;
-            sb += need;
-            max_sb = std::max(max_sb, sb);
-        }
-        if (cdoc[q + 1] > first) {
-            launches.emplace_back(first, cdoc[q + 1]);
-            chunk_of_launch.push_back(q);
-        }
-    }
-    const uint64_t scratch_half = (max_sb + 255u) & ~255ull;
-    if ((rc = grow_dev(&s->scratch, &s->scratch_cap, s->ks ? 2 * scratch_half : scratch_half))) return rc;
-    // 2. capacity (compaction is stream-ordered after every earlier batch)
-    if ((rc = ensure_space(s, bound, floor))) return rc;
-    // 3. upload + kernels
-    if ((rc = grow_dev(&R.djson, &R.djson_cap, jbytes)) ||
-        (rc = grow_dev(&R.dmeta, &R.dmeta_cap, meta_bytes)) || (rc = grow_dev(&R.douts, &R.docs_cap, nd + 1)))
+    if (B.nd) store_zero_copy(s, B);
+    B.jbytes += kTokSlack;
+    return GPUDIFF_OK;
+}
+
+// the batch's device buffers and events
+int grow_batch_buffers(DStore* s, Ring& R, const BatchTables& B, size_t n, bool strs, bool timing) {
+    int rc;
+    if ((rc = grow_dev(&R.djson, &R.djson_cap, B.jbytes)) || (rc = grow_dev(&R.dmeta, &R.dmeta_cap, B.meta_bytes)) ||
+        (rc = grow_dev(&R.douts, &R.docs_cap, B.nd + 1)) || (rc = grow_dev(&R.dcoll, &R.coll_cap, B.nd + 1)) ||
+        (rc = grow_dev(&R.ddef, &R.def_cap, n + 1)))
         return rc;
-    if ((rc = grow_dev(&R.dcoll, &R.coll_cap, nd + 1)) || (rc = grow_dev(&R.ddef, &R.def_cap, n + 1))) return rc;
-    const bool strs = (c->flags & GPUDIFF_OPT_PATH_STRINGS) != 0;
     if (strs && (rc = grow_dev(&R.dntab, &R.ntab_cap, 2 * (uint64_t)n + 2))) return rc;
-    hipStream_t st = c->stream, cs = s->cs;
-    hipStream_t k0s = dec ? s->ks0 : st;  // the K0 stage's stream (even chunks, K0c, K0x)
     if (timing && !R.t_ev[0])
         for (auto& e : R.t_ev) HIPCHK(hipEventCreate(&e));
     if (!R.chunk_ev[0])
         for (auto& e : R.chunk_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    // the upload runs on the copy stream, behind this ring slot's previous K0 (which read the
-    // same device buffers), so it overlaps the other batch's K0 / diff pass
-    if (R.k0_recorded) HIPCHK(hipStreamWaitEvent(cs, R.k0_done, 0));
-    if (timing) HIPCHK(hipEventRecord(R.t_ev[0], cs));
-    // the tables' used parts only (their device offsets are sized for 2n documents)
-    HIPCHK(hipMemcpyAsync(R.dmeta, R.hmeta, (uint64_t)nd * sizeof(TokDoc), hipMemcpyHostToDevice, cs));
-    HIPCHK(hipMemcpyAsync(R.dmeta + max_docs * sizeof(TokDoc), R.hmeta + max_docs * sizeof(TokDoc),
-                          (uint64_t)nd * sizeof(DocLink), hipMemcpyHostToDevice, cs));
-    HIPCHK(hipMemcpyAsync(R.dmeta + max_docs * (sizeof(TokDoc) + sizeof(DocLink)),
-                          R.hmeta + max_docs * (sizeof(TokDoc) + sizeof(DocLink)), 4ull * nh + 4,
-                          hipMemcpyHostToDevice, cs));
-    // One run of the workers over all chunks: worker t copies its share of chunk 0, then of chunk
-    // 1, ... and counts each chunk done; the calling thread (worker 0) enqueues a chunk's upload as
-    // soon as every worker has counted it, then goes on with its own share of the next chunk.
-    const uint32_t T = (uint32_t)std::min<uint64_t>(std::max(1u, c->threads), std::max<uint64_t>(1, jbytes >> 20));
-    std::atomic<uint32_t> chunk_done[kMaxUpChunks];
-    for (auto& x : chunk_done) x.store(0, std::memory_order_relaxed);
-    std::atomic<int> up_err{0};
-    uint32_t uploaded = 0;
-    if (dec) {  // what this batch's K0 stage reuses: the slot table (the previous batch's K0x read it) and this
-                // ring slot's space, douts and rows (its previous batch's diff pass read them)
-        if (s->last_ring >= 0 && s->ring[s->last_ring].k0_recorded)
-            HIPCHK(hipStreamWaitEvent(k0s, s->ring[s->last_ring].k0_done, 0));
-        if (R.pass_recorded) HIPCHK(hipStreamWaitEvent(k0s, R.pass_done, 0));
-        if (s->pair_mode) HIPCHK(hipMemsetAsync(s->used_dev, 0, 8, k0s));
-        if (s->st_slot_ops) {  // store mode: a compaction, Delete or placement since the last K0 stage
-            HIPCHK(hipEventRecord(s->st_ev, st));
-            HIPCHK(hipStreamWaitEvent(k0s, s->st_ev, 0));
-            s->st_slot_ops = false;
-        }
-    }
-    if (s->pair_mode) HIPCHK(hipMemsetAsync(s->slots, 0, sizeof(DSlot) * n, k0s));  // every pair starts empty
-    if (s->ks) {  // the second K0 stream starts behind everything before this batch's K0 on the K0 stage's stream
-        HIPCHK(hipEventRecord(s->ks_ev, k0s));
-        HIPCHK(hipStreamWaitEvent(s->ks, s->ks_ev, 0));
-    }
-    const TokDoc* ddocs = (const TokDoc*)R.dmeta;
-    const DocLink* dlinks = (const DocLink*)(R.dmeta + max_docs * sizeof(TokDoc));
-    const uint32_t* dheads = (const uint32_t*)(R.dmeta + max_docs * (sizeof(TokDoc) + sizeof(DocLink)));
-    uint8_t* space = s->space[s->cur];
+    return GPUDIFF_OK;
+}
+
+// One chunk's way to the device: its H2D on the copy stream, then its K0 launches behind the copy's event -- on
+// the kernel stream as soon as the upload is enqueued, so K0 of chunk q runs while chunk q + 1 is on the link,
+// not after the host has staged them all.  Called in chunk order from one thread.
+struct ChunkUploader {
+    DStore* s;
+    Ring& R;
+    const UploadPlan& P;
+    const uint8_t* hsrc;    // the staged layout: R.hjson, or the caller's buffer (zero copy)
+    bool zero_copy;
+    hipStream_t cs, k0s;    // the copy stream; the K0 stage's stream (even chunks, K0c, K0x)
+    uint64_t scratch_half;  // each K0 stream's part of the scratch
+    const TokDoc* ddocs;
+    const DocLink* dlinks;
+    bool timing;
     size_t li = 0;  // next K0 launch
-    // chunk q's K0 launches go on the kernel stream as soon as its upload is enqueued (behind its copy
-    // event), so K0 of chunk q runs while chunk q + 1 is on the link -- not after the host has staged them all
-    auto upload = [&](uint32_t q) {
-        const uint64_t b0 = cbyte(q), b1 = cbyte(q + 1);
-        if (!zsrc && q + 1 == C && cdoc[q] >= nd) memset(R.hjson + b0, 0, b1 - b0);  // no documents: the slack only
+    std::atomic<int> err{0};
+
+    void upload(uint32_t q) {
+        const uint64_t b0 = P.cbyte(q), b1 = P.cbyte(q + 1);
+        if (!zero_copy && q + 1 == P.C && P.cdoc[q] >= P.nd) memset(R.hjson + b0, 0, b1 - b0);  // the slack only
         hipStream_t qs = cs;  // one DMA queue saturates the link (two measured slower, profiles/r04z)
         const bool odd = (q & 1u) != 0u;
         hipStream_t kq = odd ? s->ks : k0s;  // this chunk's K0 stream, and its half of the scratch
@@ -1177,68 +1033,123 @@ int dstore_submit(gpudiff_ctx* c, DStore* s, const gpudiff_event* ev, size_t n, 
         if (hipMemcpyAsync(R.djson + b0, hsrc + b0, b1 - b0, hipMemcpyHostToDevice, qs) != hipSuccess ||
             hipEventRecord(R.chunk_ev[q], qs) != hipSuccess || hipStreamWaitEvent(kq, R.chunk_ev[q], 0) != hipSuccess ||
             (q == 0 && timing && hipEventRecord(R.t_ev[2], k0s) != hipSuccess)) {
-            up_err.store(1);
+            err.store(1);
             return;
         }
-        for (; li < launches.size() && chunk_of_launch[li] == q; li++) {
-            const auto& L = launches[li];
-            if (launch_encode_docs(kq, ddocs + L.first, L.second - L.first, R.djson, scr, space, s->space_bytes,
-                                   s->used_dev, c->hash_mask, R.douts + L.first, s->slots, dlinks + L.first) !=
-                hipSuccess) {
-                up_err.store(1);
+        for (; li < P.launches.size() && P.chunk_of_launch[li] == q; li++) {
+            const auto& L = P.launches[li];
+            if (launch_encode_docs(kq, ddocs + L.first, L.second - L.first, R.djson, scr, s->space[s->cur],
+                                   s->space_bytes, s->used_dev, s->c->hash_mask, R.douts + L.first, s->slots,
+                                   dlinks + L.first) != hipSuccess) {
+                err.store(1);
                 return;
             }
         }
-    };
-    if (zsrc)  // nothing to stage: every chunk's upload (and its K0 launches) goes out at once
-        while (uploaded < C) upload(uploaded++);
-    else
-    workers(c).run(T, [&](uint32_t t) {
-        for (uint32_t q = 0; q < C; q++) {
-            const uint64_t b0 = cbyte(q), b1 = cbyte(q + 1);
-            const uint32_t k0 = std::max(cdoc[q], first_doc(b0 + (b1 - b0) * t / T));
-            const uint32_t k1 = std::min(cdoc[q + 1], first_doc(b0 + (b1 - b0) * (t + 1) / T));
-            for (uint32_t k = k0; k < k1; k++) {
-                const uint64_t o = docs[k].json_off;
-                const uint64_t end = k + 1 < nd ? docs[k + 1].json_off : jbytes;
-                stream_doc(R.hjson + o, src[k], docs[k].json_len, end - o);
-            }
-            _mm_sfence();  // the streaming stores are visible before the chunk counts as done
-            chunk_done[q].fetch_add(1, std::memory_order_release);
-            if (t == 0)  // upload every chunk all workers have finished, in order, without waiting
-                while (uploaded <= q && chunk_done[uploaded].load(std::memory_order_acquire) >= T) upload(uploaded++);
-        }
-        if (t == 0)
-            while (uploaded < C) {
-                if (chunk_done[uploaded].load(std::memory_order_acquire) < T) {
-                    std::this_thread::yield();
-                    continue;
+    }
+};
+
+// The stream ordering of the batch's upload and K0 stage, the three table copies, the staging copy by the workers
+// with each chunk uploaded (and its K0 launched) as soon as it is staged, and R.staged behind the last copy.
+int stage_and_encode(DStore* s, Ring& R, const BatchTables& B, const UploadPlan& P, size_t n, bool dec,
+                     uint64_t scratch_half, bool timing, Lap& lap) {
+    gpudiff_ctx* c = s->c;
+    hipStream_t cs = s->cs;
+    hipStream_t k0s = dec ? s->ks0 : c->stream;
+    // the upload runs on the copy stream, behind this ring slot's previous K0 (which read the
+    // same device buffers), so it overlaps the other batch's K0 / diff pass
+    if (R.k0_recorded) HIPCHK(hipStreamWaitEvent(cs, R.k0_done, 0));
+    if (timing) HIPCHK(hipEventRecord(R.t_ev[0], cs));
+    // the tables' used parts only (their device offsets are sized for 2n documents)
+    HIPCHK(hipMemcpyAsync(R.dmeta, R.hmeta, (uint64_t)B.nd * sizeof(TokDoc), hipMemcpyHostToDevice, cs));
+    HIPCHK(hipMemcpyAsync(R.dmeta + B.links_off(), R.hmeta + B.links_off(), (uint64_t)B.nd * sizeof(DocLink),
+                          hipMemcpyHostToDevice, cs));
+    HIPCHK(hipMemcpyAsync(R.dmeta + B.heads_off(), R.hmeta + B.heads_off(), 4ull * B.nh + 4, hipMemcpyHostToDevice,
+                          cs));
+    if (dec) {  // what this batch's K0 stage reuses: the slot table (the previous batch's K0x read it) and this
+                // ring slot's space, douts and rows (its previous batch's diff pass read them)
+        if (s->last_ring >= 0 && s->ring[s->last_ring].k0_recorded)
+            HIPCHK(hipStreamWaitEvent(k0s, s->ring[s->last_ring].k0_done, 0));
+        if (R.pass_recorded) HIPCHK(hipStreamWaitEvent(k0s, R.pass_done, 0));
+        HIPCHK(hipMemsetAsync(s->used_dev, 0, 8, k0s));
+    }
+    if (s->pair_mode) HIPCHK(hipMemsetAsync(s->slots, 0, sizeof(DSlot) * n, k0s));  // every pair starts empty
+    if (s->ks) {  // the second K0 stream starts behind everything before this batch's K0 on the K0 stage's stream
+        HIPCHK(hipEventRecord(s->ks_ev, k0s));
+        HIPCHK(hipStreamWaitEvent(s->ks, s->ks_ev, 0));
+    }
+    ChunkUploader up{s, R, P, B.zsrc ? B.zsrc : R.hjson, B.zsrc != nullptr, cs, k0s, scratch_half,
+                     (const TokDoc*)R.dmeta, (const DocLink*)(R.dmeta + B.links_off()), timing};
+    uint32_t uploaded = 0;
+    if (B.zsrc) {  // nothing to stage: every chunk's upload (and its K0 launches) goes out at once
+        while (uploaded < P.C) up.upload(uploaded++);
+    } else {
+        // One run of the workers over all chunks: worker t copies its share of chunk 0, then of chunk
+        // 1, ... and counts each chunk done; the calling thread (worker 0) enqueues a chunk's upload as
+        // soon as every worker has counted it, then goes on with its own share of the next chunk.
+        const uint32_t T =
+            (uint32_t)std::min<uint64_t>(std::max(1u, c->threads), std::max<uint64_t>(1, B.jbytes >> 20));
+        std::atomic<uint32_t> chunk_done[kMaxUpChunks];
+        for (auto& x : chunk_done) x.store(0, std::memory_order_relaxed);
+        uint8_t* hjson = R.hjson;
+        workers(c).run(T, [&up, &P, &B, &chunk_done, &uploaded, hjson, T](uint32_t t) {
+            for (uint32_t q = 0; q < P.C; q++) {
+                const uint64_t b0 = P.cbyte(q), b1 = P.cbyte(q + 1);
+                const uint32_t k0 = std::max(P.cdoc[q], P.first_doc(b0 + (b1 - b0) * t / T));
+                const uint32_t k1 = std::min(P.cdoc[q + 1], P.first_doc(b0 + (b1 - b0) * (t + 1) / T));
+                for (uint32_t k = k0; k < k1; k++) {
+                    const uint64_t o = B.docs[k].json_off;
+                    const uint64_t end = k + 1 < B.nd ? B.docs[k + 1].json_off : B.jbytes;
+                    stream_doc(hjson + o, B.src[k], B.docs[k].json_len, end - o);
                 }
-                upload(uploaded++);
+                _mm_sfence();  // the streaming stores are visible before the chunk counts as done
+                chunk_done[q].fetch_add(1, std::memory_order_release);
+                if (t == 0)  // upload every chunk all workers have finished, in order, without waiting
+                    while (uploaded <= q && chunk_done[uploaded].load(std::memory_order_acquire) >= T)
+                        up.upload(uploaded++);
             }
-    });
-    if (up_err.load()) return GPUDIFF_E_DEVICE;
+            if (t == 0)
+                while (uploaded < P.C) {
+                    if (chunk_done[uploaded].load(std::memory_order_acquire) < T) {
+                        std::this_thread::yield();
+                        continue;
+                    }
+                    up.upload(uploaded++);
+                }
+        });
+    }
+    if (up.err.load()) return GPUDIFF_E_DEVICE;
     lap(2);
     HIPCHK(hipEventRecord(R.staged, cs));
     if (timing) HIPCHK(hipEventRecord(R.t_ev[1], cs));
-    if (li != launches.size()) return GPUDIFF_E_STATE;  // every launch belongs to an uploaded chunk
+    if (up.li != P.launches.size()) return GPUDIFF_E_STATE;  // every launch belongs to an uploaded chunk
+    return GPUDIFF_OK;
+}
+
+// K0c and K0x behind every chunk's K0, then the ordinary diff pass over the batch's rows
+int link_and_diff(DStore* s, Ring& R, const BatchTables& B, size_t n, uint32_t batch, bool dec, bool strs, bool timing,
+                  gpudiff_ticket* ticket) {
+    gpudiff_ctx* c = s->c;
+    hipStream_t st = c->stream;
+    hipStream_t k0s = dec ? s->ks0 : st;
+    const DocLink* dlinks = (const DocLink*)(R.dmeta + B.links_off());
+    const uint32_t* dheads = (const uint32_t*)(R.dmeta + B.heads_off());
+    uint8_t* space = s->space[s->cur];
     if (s->ks) {  // K0c waits for the odd chunks' K0 too
         HIPCHK(hipEventRecord(s->ks_ev, s->ks));
         HIPCHK(hipStreamWaitEvent(k0s, s->ks_ev, 0));
     }
     HIPCHK(hipStreamWaitEvent(k0s, R.staged, 0));  // every chunk (and the tables) landed
     if (timing) HIPCHK(hipEventRecord(R.t_ev[3], k0s));
-    HIPCHK(launch_collide(k0s, dlinks, R.douts, s->slots, nd, space, R.dcoll));
+    HIPCHK(launch_collide(k0s, dlinks, R.douts, s->slots, B.nd, space, R.dcoll));
     HIPCHK(hipMemsetAsync(R.dcnt, 0, 4, k0s));
     gpudiff_dbatch* d = R.d;
-    HIPCHK(launch_link(k0s, dheads, nh, dlinks, R.douts, R.dcoll, s->slots, d->rows, d->pair_ids, R.ddef, batch,
+    HIPCHK(launch_link(k0s, dheads, B.nh, dlinks, R.douts, R.dcoll, s->slots, d->rows, d->pair_ids, R.ddef, batch,
                        R.dcnt, s->ctr, strs ? R.dntab : nullptr));
     HIPCHK(hipEventRecord(R.k0_done, k0s));
     R.k0_recorded = true;
     if (timing) HIPCHK(hipEventRecord(R.t_ev[4], k0s));
     if (dec) HIPCHK(hipStreamWaitEvent(st, R.k0_done, 0));  // the diff pass reads the rows K0x wrote
-    s->used_ub += bound;
-    // 4. the diff pass over the batch's rows
+    s->used_ub += B.bound;
     d->pool = space;
     d->pool_cap = s->space_bytes;
     d->pool_used = s->used_ub;
@@ -1246,8 +1157,8 @@ int dstore_submit(gpudiff_ctx* c, DStore* s, const gpudiff_event* ev, size_t n, 
     d->rows_gen++;
     d->leaves = 0;
     d->compare_bytes = d->value_bytes = 0;
-    d->size_hint_bytes = 2 * new_json_bytes;  // k2_sub_shift's size class (engine.h)
-    if ((rc = gpudiff_diff(c, d, ticket))) {
+    d->size_hint_bytes = 2 * B.new_json_bytes;  // k2_sub_shift's size class (engine.h)
+    if (int rc = gpudiff_diff(c, d, ticket)) {
         s->broken = true;
         return rc;
     }
@@ -1255,72 +1166,116 @@ int dstore_submit(gpudiff_ctx* c, DStore* s, const gpudiff_event* ev, size_t n, 
         HIPCHK(hipEventRecord(R.pass_done, st));
         R.pass_recorded = true;
     }
+    return GPUDIFF_OK;
+}
+
+// gpudiff_wait on the batch's ticket, after collect_results: the exact append point, the phase timings, the
+// changed paths as text, the host resolution of what K0 deferred
+int finish_batch(DStore* s, Ring& R, ResultStore& rs) {
+    const auto t_fin0 = std::chrono::steady_clock::now();
+    gpudiff_ctx* c = s->c;
+    const uint32_t ri = (uint32_t)(&R - s->ring);
+    R.outstanding = false;
+    if (!s->pair_mode) {
+        if (R.batch != s->next_wait) return GPUDIFF_E_STATE;  // waits follow submit order
+        s->next_wait++;
+    }
+    uint32_t ndef = 0;
+    uint64_t used = 0;
+    if (s->pair_mode) {  // resolution appends to this batch's own space
+        s->cur = ri;
+        s->used_dev = s->used_base + s->cur;
+    }
+    HIPCHK(hipMemcpyAsync(&ndef, R.dcnt, 4, hipMemcpyDeviceToHost, c->rb));  // behind K0x: d->done waited
+    HIPCHK(hipMemcpyAsync(&used, s->used_dev, 8, hipMemcpyDeviceToHost, c->rb));
+    HIPCHK(hipStreamSynchronize(c->rb));
+    // exact append point + what the other batch in flight may still add
+    const Ring& other = s->ring[ri ^ 1u];
+    s->used_ub = s->pair_mode ? used : std::max<uint64_t>(used, used + (other.outstanding ? other.bound : 0));
+    if (R.t_ev[0] && (c->flags & GPUDIFF_OPT_TIMING)) {
+        float ms[3];
+        HIPCHK(hipEventElapsedTime(&ms[0], R.t_ev[0], R.t_ev[1]));  // H2D
+        HIPCHK(hipEventElapsedTime(&ms[1], R.t_ev[2], R.t_ev[3]));  // K0
+        HIPCHK(hipEventElapsedTime(&ms[2], R.t_ev[3], R.t_ev[4]));  // K0c + K0x
+        for (int k = 0; k < 3; k++) s->t_sum[1 + k] += ms[k];
+        s->t_n++;
+    }
+    // the strings before resolve(): its compaction may pack into the space this batch's superseded blobs are in
+    int rc = R.strs ? render_paths(s, R, rs) : GPUDIFF_OK;
+    if (!rc && ndef) rc = resolve(s, R, rs);
+    if (!rc && R.strs) {
+        c->path_stats.paths += rs.ps.n;
+        c->path_stats.bytes += rs.ps.offsets()[rs.ps.n];
+        c->path_stats.host_paths += rs.ps.n_host;
+    }
+    if (rc) s->broken = true;
+    if (!rc && s->pair_mode) {  // kept for gpudiff_write_plan_get
+        R.final_flags.assign(rs.flags.begin(), rs.flags.end());
+        R.waited = true;
+    }
+    // forgets older than every outstanding batch are settled
+    for (auto it = s->forgotten.begin(); it != s->forgotten.end();)
+        it = it->second < s->next_wait ? s->forgotten.erase(it) : std::next(it);
+    s->t_sub[4] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_fin0).count();
+    return rc;
+}
+
+}  // namespace
+
+int dstore_submit(gpudiff_ctx* c, DStore* s, const gpudiff_event* ev, size_t n, gpudiff_ticket* ticket) {
+    if (s->broken) return GPUDIFF_E_STATE;
+    if (n > s->max_events) return GPUDIFF_E_INVAL;
+    if (refuse_if_strings_need_compaction(s, ev, n)) return GPUDIFF_E_STATE;
+    const auto t_host0 = std::chrono::steady_clock::now();
+    const bool timing = (c->flags & GPUDIFF_OPT_TIMING) != 0;
+    const bool strs = (c->flags & GPUDIFF_OPT_PATH_STRINGS) != 0;
+    // pair mode runs the K0 stage on its own streams (ks0 / ks), decoupled from the kernel stream
+    const bool dec = s->pair_mode && s->ks0;
+    int rc;
+    Ring* Rp = nullptr;
+    if ((rc = claim_ring_slot(s, dec, &Rp))) return rc;
+    Ring& R = *Rp;
+    Lap lap{timing, s->t_sub};
+    lap(0);
+    const uint32_t batch = ++s->batch_seq;
+
+    // 1. documents and slot chains
+    BatchTables B;
+    if ((rc = map_tables(R, n, B))) return rc;
+    if ((rc = (s->pair_mode ? build_tables_pairs : build_tables_store)(s, ev, n, batch, B))) return rc;
+    if (!B.zsrc && (rc = grow_pinned(&R.hjson, &R.hjson_cap, B.jbytes))) return rc;
+    lap(1);
+    const UploadPlan P = plan_upload(B.docs, B.nd, B.jbytes);
+    const uint64_t scratch_half = (P.max_sb + 255u) & ~255ull;
+    if ((rc = grow_dev(&s->scratch, &s->scratch_cap, s->ks ? 2 * scratch_half : scratch_half))) return rc;
+    // 2. capacity (compaction is stream-ordered after every earlier batch)
+    if ((rc = ensure_space(s, B.bound, B.floor))) return rc;
+    // 3. upload + kernels
+    if ((rc = grow_batch_buffers(s, R, B, n, strs, timing))) return rc;
+    if ((rc = stage_and_encode(s, R, B, P, n, dec, scratch_half, timing, lap))) return rc;
+    // 4. the links, and the diff pass over the batch's rows
+    if ((rc = link_and_diff(s, R, B, n, batch, dec, strs, timing, ticket))) return rc;
+
     s->last_ring = (int)(&R - s->ring);
     R.events.assign(ev, ev + n);
     R.waited = false;
     R.batch = batch;
     R.nev = (uint32_t)n;
-    R.bound = bound;
+    R.bound = B.bound;
     R.strs = strs;
     R.space_idx = s->cur;
     R.ticket = *ticket;
     R.outstanding = true;
-    Ring* Rp = &R;
-    c->finishers[*ticket] = [s, Rp](ResultStore& rs) -> int {
-        const auto t_fin0 = std::chrono::steady_clock::now();
-        Ring& RR = *Rp;
-        RR.outstanding = false;
-        if (!s->pair_mode) {
-            if (RR.batch != s->next_wait) return GPUDIFF_E_STATE;  // waits follow submit order
-            s->next_wait++;
-        }
-        uint32_t ndef = 0;
-        uint64_t used = 0;
-        if (s->pair_mode) {  // resolution appends to this batch's own space
-            s->cur = (uint32_t)(Rp - s->ring);
-            s->used_dev = s->used_base + s->cur;
-        }
-        HIPCHK(hipMemcpyAsync(&ndef, RR.dcnt, 4, hipMemcpyDeviceToHost, s->c->rb));  // behind K0x: d->done waited
-        HIPCHK(hipMemcpyAsync(&used, s->used_dev, 8, hipMemcpyDeviceToHost, s->c->rb));
-        HIPCHK(hipStreamSynchronize(s->c->rb));
-        // exact append point + what the other batch in flight may still add
-        const Ring& other = s->ring[(Rp - s->ring) ^ 1];
-        s->used_ub = s->pair_mode ? used : std::max<uint64_t>(used, used + (other.outstanding ? other.bound : 0));
-        if (RR.t_ev[0] && (s->c->flags & GPUDIFF_OPT_TIMING)) {
-            float ms[3];
-            HIPCHK(hipEventElapsedTime(&ms[0], RR.t_ev[0], RR.t_ev[1]));  // H2D
-            HIPCHK(hipEventElapsedTime(&ms[1], RR.t_ev[2], RR.t_ev[3]));  // K0
-            HIPCHK(hipEventElapsedTime(&ms[2], RR.t_ev[3], RR.t_ev[4]));  // K0c + K0x
-            for (int k = 0; k < 3; k++) s->t_sum[1 + k] += ms[k];
-            s->t_n++;
-        }
-        // the strings before resolve(): its compaction may pack into the space this batch's superseded blobs are in
-        int r2 = RR.strs ? render_paths(s, RR, rs) : GPUDIFF_OK;
-        if (!r2 && ndef) r2 = resolve(s, RR, rs);
-        if (!r2 && RR.strs) {
-            s->c->path_stats.paths += rs.ps.n;
-            s->c->path_stats.bytes += rs.ps.offsets()[rs.ps.n];
-            s->c->path_stats.host_paths += rs.ps.n_host;
-        }
-        if (r2) s->broken = true;
-        if (!r2 && s->pair_mode) {  // kept for gpudiff_write_plan_get
-            RR.final_flags.assign(rs.flags.begin(), rs.flags.end());
-            RR.waited = true;
-        }
-        // forgets older than every outstanding batch are settled
-        for (auto it = s->forgotten.begin(); it != s->forgotten.end();)
-            it = it->second < s->next_wait ? s->forgotten.erase(it) : std::next(it);
-        s->t_sub[4] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_fin0).count();
-        return r2;
-    };
+    c->finishers[*ticket] = [s, Rp](ResultStore& rs) -> int { return finish_batch(s, *Rp, rs); };
     s->ring_next ^= 1u;
     lap(3);
     if (timing)
         s->t_sum[0] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_host0).count();
     s->st.events += n;
-    s->st.last_batch_bytes = jbytes;
+    s->st.last_batch_bytes = B.jbytes;
     return GPUDIFF_OK;
 }
+
 
 int dstore_submit_pairs(gpudiff_ctx* c, const gpudiff_json_pair* pairs, size_t n, gpudiff_ticket* ticket) {
     DStore*& s = c->pair_store;
@@ -1404,7 +1359,6 @@ void dstore_host_bufs_release(gpudiff_ctx* c) {
 }
 
 int dstore_forget(gpudiff_ctx* c, DStore* s, uint32_t slot) {
-    if (int rc = before_st_slot_op(s)) return rc;
     HIPCHK(launch_forget(c->stream, s->slots, slot, s->ctr));
     s->seen[slot] = 0;
     s->forgotten[slot] = s->batch_seq;
@@ -1470,7 +1424,6 @@ void dstore_free(gpudiff_ctx* c, DStore* s) {
         }
     for (Ring& R : s->ring)
         if (R.pass_done) (void)hipEventDestroy(R.pass_done);
-    if (s->st_ev) (void)hipEventDestroy(s->st_ev);
     if (s->ks_ev) (void)hipEventDestroy(s->ks_ev);
     if (s->cs) {
         (void)hipStreamSynchronize(s->cs);
@@ -1489,8 +1442,6 @@ int dstore_staged_pairs(gpudiff_ctx* c, gpudiff_ticket t, StagedPairs* out) {
     for (Ring& R : s->ring) {
         if (R.ticket != t) continue;
         if (!R.waited || R.outstanding) return GPUDIFF_E_STATE;  // gpudiff_wait first
-        const uint64_t max_docs = 2 * (uint64_t)R.nev;
-        (void)max_docs;
         out->hdocs = (const TokDoc*)R.hmeta;
         out->djson = R.djson;
         out->n = R.nev;

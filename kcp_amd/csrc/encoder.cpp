@@ -471,6 +471,48 @@ bool PairEncoder::pair_seed(FlatObject& a, FlatObject& b, uint32_t* seed) {
     return true;
 }
 
+StoreDecision PairEncoder::store_decide(bool live, uint32_t slot_seed, ResidentTabFn resident_tab, void* ctx,
+                                        const uint8_t* old_json, size_t old_len, const uint8_t* new_json,
+                                        size_t new_len, Arena& arena_old, Arena& arena_new, FlatObject& fo,
+                                        FlatObject& fn) {
+    StoreDecision d;
+    if (!flatten_json(new_json, new_len, arena_new, fn)) return d;  // nothing to store
+    d.store_ok = true;
+    const PathTable* tab = nullptr;
+    if (live && slot_seed == 0) {  // the common case: the resident version is the old side as it stands
+        if ((d.rc = resident_tab(ctx, &tab))) return d;
+        if (hash_single(fn, 0) && tab_agree(tab_view(*tab), tab_view(fn.tab))) {
+            d.rung = StoreRung::kResidentSeed0;
+            return d;
+        }
+    }
+    if (old_json) {  // first sighting, a re-seeded slot, or a collision: encode the pair from old_json
+        if (flatten_json(old_json, old_len, arena_old, fo) && pair_seed(fo, fn, &d.seed)) {
+            d.rung = StoreRung::kReencodedOld;
+            d.old_encoded = 1;
+            d.reseeded = live ? 1 : 0;
+            return d;
+        }  // else an undecodable old object or no valid seed: as gpudiff_encode_pairs
+    } else if (live && slot_seed) {  // re-seeded earlier and no old object to re-encode: keep its seed
+        if ((d.rc = resident_tab(ctx, &tab))) return d;
+        if (hash_single(fn, slot_seed) && tab_agree(tab_view(*tab), tab_view(fn.tab))) {
+            d.rung = StoreRung::kResidentSlotSeed;
+            d.seed = slot_seed;
+            return d;
+        }
+        d.unresolved = 1;
+    } else if (!live) {  // first sighting without an old object: diff against the empty object {}
+        if (first_seed(fn, &d.seed)) {
+            d.rung = StoreRung::kFirstSighting;
+            return d;
+        }
+    } else {
+        d.unresolved = 1;
+    }
+    d.store_ok = store_seed(fn, &d.seed);  // the new version under a self-consistent seed
+    return d;
+}
+
 void PairEncoder::write_object(const FlatObject& o, std::vector<uint8_t>& pool, uint64_t* off, uint32_t* sl,
                                uint32_t* sar, uint32_t* tl, uint32_t* tar) {
     write_blob(o, pool, off, sl, sar, tl, tar);

@@ -92,6 +92,25 @@ struct EncodeConfig {
 // Flattens a decoded top-level object into its spec/status leaves.
 void flatten_object(const Node& root, FlatObject& out);
 
+// The object store's decision for one event on a slot (PairEncoder::store_decide): which old side the new object
+// is diffed against.  The rungs are tried in this order.
+enum class StoreRung : uint8_t {
+    kResidentSeed0,     // the resident blob as it stands (seed 0, its path table agrees with the new object's)
+    kReencodedOld,      // the pair re-encoded from old_json: `fo` is the old side, hashed under `seed`
+    kResidentSlotSeed,  // a slot re-seeded earlier and no old_json: the resident blob at the slot's seed
+    kFirstSighting,     // no resident version and no old_json: diffed against the empty object
+    kPairError,         // none of them: the event is reported conservatively
+};
+struct StoreDecision {
+    StoreRung rung = StoreRung::kPairError;
+    uint32_t seed = 0;      // what `fn` is hashed under now
+    bool store_ok = false;  // `fn` (with fn.tab) can be stored under `seed`; false: the slot is emptied
+    uint32_t old_encoded = 0, reseeded = 0, unresolved = 0;  // counter deltas
+    int rc = 0;  // the resident table's error, passed through (nothing else is set then)
+};
+// The slot's resident path table, asked for only by the rungs that read it (the device store fetches it then)
+using ResidentTabFn = int (*)(void* ctx, const PathTable** tab);
+
 class PairEncoder {
    public:
     explicit PairEncoder(const EncodeConfig& cfg) : cfg_(cfg) {}
@@ -124,6 +143,13 @@ class PairEncoder {
     // fills b.tab (GPUDIFF_TAB_NONE if b's table is not valid under that
     // seed).  False if no seed <= 255 works.
     bool pair_seed(FlatObject& a, FlatObject& b, uint32_t* seed);
+    // One event of the object store on a slot that is `live` with `slot_seed`: flattens new_json into fn (and
+    // old_json into fo where the ladder re-encodes the pair) and picks the rung and the seed.  The encoder calls
+    // keep this order -- each re-hashes fn: hash_single(fn, 0), pair_seed, hash_single(fn, slot_seed),
+    // first_seed, store_seed.
+    StoreDecision store_decide(bool live, uint32_t slot_seed, ResidentTabFn resident_tab, void* ctx,
+                               const uint8_t* old_json, size_t old_len, const uint8_t* new_json, size_t new_len,
+                               Arena& arena_old, Arena& arena_new, FlatObject& fo, FlatObject& fn);
     // o.tab for the region leaves' paths under `seed` (false, and n =
     // GPUDIFF_TAB_NONE: not valid)
     bool path_table(FlatObject& o, uint32_t seed);

@@ -165,64 +165,41 @@ static void store_encode_part(gpudiff_ctx* c, gpudiff_store* s, const gpudiff_ev
         memset(&r, 0, sizeof(r));
         r.pair_id = e.pair_id;
         r.cluster_id = e.cluster_id;
-        auto conservative = [&]() {  // reported dirty in both regions, no paths (specsyncer.go:20-22)
-            r.flags_a = r.flags_b = GPUDIFF_OBJ_DECODE_ERR;
-            r.off_a = r.off_b = 0;
-        };
-        if (!enc.flatten_json(e.new_json, e.new_len, w.arena_new, w.fn)) {
-            conservative();
+        // which old side, and under which seed (the ladder the device store's host resolution shares)
+        const StoreDecision D = enc.store_decide(
+            S.live, S.seed, [](void* tab, const PathTable** out) { return *out = (const PathTable*)tab, 0; }, &S.tab,
+            e.old_json, e.old_len, e.new_json, e.new_len, w.arena_old, w.arena_new, w.fo, w.fn);
+        const bool pair_error = D.rung == StoreRung::kPairError;
+        const uint32_t seed = D.seed;
+        w.old_encoded += D.old_encoded;
+        w.reseeded += D.reseeded;
+        w.unresolved += D.unresolved;
+        // reported dirty in both regions, no paths (specsyncer.go:20-22)
+        if (pair_error) r.flags_a = r.flags_b = GPUDIFF_OBJ_DECODE_ERR;
+        if (!D.store_ok) {  // undecodable, or no seed it could be stored under
             S.live = false;
             S.tab.clear();
             continue;
         }
         Blob A{0, 0, 0, 0, 0, 0, 0, false};
-        uint32_t seed = 0;
-        bool ok = false, pair_error = false;
-        if (S.live && S.seed == 0 && enc.hash_single(w.fn, 0) && tab_agree(tab_view(S.tab), tab_view(w.fn.tab))) {
-            ok = true;  // the common case: the resident version is the old side as it stands
+        if (D.rung == StoreRung::kResidentSeed0 || D.rung == StoreRung::kResidentSlotSeed) {
             A = Blob{S.off, S.bytes, S.spec_l, S.spec_ar, S.stat_l, S.stat_ar, S.oflags, false};
-        } else if (e.old_json) {
-            // first sighting, a re-seeded slot, or a collision: encode the pair from old_json
-            if (enc.flatten_json(e.old_json, e.old_len, w.arena_old, w.fo) && enc.pair_seed(w.fo, w.fn, &seed)) {
-                uint64_t off;
-                A.fresh = true;
-                enc.write_object(w.fo, w.pool, &off, &A.spec_l, &A.spec_ar, &A.stat_l, &A.stat_ar);
-                A.off = local_tag(t, off);
-                A.bytes = blob_bytes(A.spec_l, A.spec_ar, A.stat_l, A.stat_ar);
-                A.oflags = w.fo.flags;
-                w.leaves += w.fo.spec.size() + w.fo.stat.size();
-                w.old_encoded++;
-                if (S.live) w.reseeded++;
-                ok = true;
-            } else {
-                pair_error = true;  // undecodable old object or no valid seed: as gpudiff_encode_pairs
-            }
-        } else if (S.live && S.seed && enc.hash_single(w.fn, S.seed) &&
-                   tab_agree(tab_view(S.tab), tab_view(w.fn.tab))) {
-            ok = true;  // slot re-seeded earlier and no old object to re-encode: keep its seed
-            seed = S.seed;
-            A = Blob{S.off, S.bytes, S.spec_l, S.spec_ar, S.stat_l, S.stat_ar, S.oflags, false};
-        } else if (!S.live) {
-            // first sighting without an old object: diff against the empty object {}
-            ok = enc.first_seed(w.fn, &seed);
-            pair_error = !ok;
-        } else {
-            pair_error = true;
-            w.unresolved++;
+        } else if (D.rung == StoreRung::kReencodedOld) {
+            uint64_t off;
+            A.fresh = true;
+            enc.write_object(w.fo, w.pool, &off, &A.spec_l, &A.spec_ar, &A.stat_l, &A.stat_ar);
+            A.off = local_tag(t, off);
+            A.bytes = blob_bytes(A.spec_l, A.spec_ar, A.stat_l, A.stat_ar);
+            A.oflags = w.fo.flags;
+            w.leaves += w.fo.spec.size() + w.fo.stat.size();
         }
-        // store the new version (self-consistent seed if the pair failed)
-        if (pair_error) {
-            conservative();
-            if (!enc.store_seed(w.fn, &seed)) {
-                S.live = false;
-                S.tab.clear();
-                continue;
-            }
-        }
+        // store the new version (self-consistent seed if the pair failed); a conservative row reads nothing
+        // (decode error), it still names the stored blob, on its own side only (flags_b FRESH with zero-length A)
         uint64_t off;
-        uint32_t sl, sar, tl, tar;
-        enc.write_object(w.fn, w.pool, &off, &sl, &sar, &tl, &tar);
+        enc.write_object(w.fn, w.pool, &off, &r.spec_l_b, &r.spec_ar_b, &r.stat_l_b, &r.stat_ar_b);
         w.leaves += w.fn.spec.size() + w.fn.stat.size();
+        r.off_b = local_tag(t, off);
+        r.flags_b = GPUDIFF_OBJ_DECODE_ERR | GPUDIFF_OBJ_FRESH;
         if (!pair_error) {
             r.off_a = A.bytes ? A.off : local_tag(t, off);  // a 0-byte blob is never read
             r.spec_l_a = A.spec_l;
@@ -230,30 +207,16 @@ static void store_encode_part(gpudiff_ctx* c, gpudiff_store* s, const gpudiff_ev
             r.stat_l_a = A.stat_l;
             r.stat_ar_a = A.stat_ar;
             r.flags_a = A.oflags | (seed << GPUDIFF_OBJ_SEED_SHIFT) | (A.fresh ? GPUDIFF_OBJ_FRESH : 0u);
-            r.off_b = local_tag(t, off);
-            r.spec_l_b = sl;
-            r.spec_ar_b = sar;
-            r.stat_l_b = tl;
-            r.stat_ar_b = tar;
             r.flags_b = w.fn.flags | (seed << GPUDIFF_OBJ_SEED_SHIFT) | GPUDIFF_OBJ_FRESH;
-        } else {
-            // the conservative row reads nothing (decode error): it still names the stored blob,
-            // on its own side only (flags_b FRESH with zero-length A)
-            r.off_b = local_tag(t, off);
-            r.spec_l_b = sl;
-            r.spec_ar_b = sar;
-            r.stat_l_b = tl;
-            r.stat_ar_b = tar;
-            r.flags_b = GPUDIFF_OBJ_DECODE_ERR | GPUDIFF_OBJ_FRESH;
         }
         S.live = true;
         S.seed = seed;
-        S.off = local_tag(t, off);
-        S.bytes = blob_bytes(sl, sar, tl, tar);
-        S.spec_l = sl;
-        S.spec_ar = sar;
-        S.stat_l = tl;
-        S.stat_ar = tar;
+        S.off = r.off_b;
+        S.spec_l = r.spec_l_b;
+        S.spec_ar = r.spec_ar_b;
+        S.stat_l = r.stat_l_b;
+        S.stat_ar = r.stat_ar_b;
+        S.bytes = blob_bytes(S.spec_l, S.spec_ar, S.stat_l, S.stat_ar);
         S.oflags = w.fn.flags & GPUDIFF_OBJ_HAS_STATUS;
         w.live_delta++;
         w.bytes_delta += S.bytes;

@@ -170,6 +170,8 @@ constexpr int64_t kZeroTimeSec = -62135596800ll;
 
 constexpr uint32_t kTokMaxLen = (1u << 24) - 64u;  // token words hold 24-bit positions
 constexpr uint32_t kTokSlack = 32u;                 // readable bytes K0 needs after each staged document
+// a staged document's span: its bytes, the slack, padded so the next document starts 16-B aligned
+constexpr uint64_t tok_staged_span(uint64_t len) { return (len + kTokSlack + 15) & ~15ull; }
 
 // ------------------------------------------------------------ device object store
 // One slot per informer-cache object: its resident blob (K0 format, with the
