@@ -273,7 +273,8 @@ int gpudiff_dbatch_device_view(const gpudiff_dbatch* db, gpudiff_device_view* v)
  * (e.g. a tensor handed to an RCCL all-gather), ordered on the context
  * stream; copies min(count, max_elems) elements of `what` */
 #define GPUDIFF_EXPORT_COUNTS 0u      /* 8 x u32: n_spec, n_status, n_dirty, K4 scratch entries (saturating),
-                                         overflow, n_paths, any join deferred to K3/K4, 0 */
+                                         overflow, n_paths, any join deferred to K3/K4, regions whose changed
+                                         paths K2 emitted from its compare stream without the merge-join */
 #define GPUDIFF_EXPORT_SPEC_IDS 1u    /* u32 */
 #define GPUDIFF_EXPORT_STATUS_IDS 2u  /* u32 */
 #define GPUDIFF_EXPORT_DIRTY_IDS 3u   /* u32 */

@@ -23,6 +23,7 @@
 
 #include "../../include/gpudiff.h"
 #include "kernels.h"
+#include "stream_paths.h"
 #include "xxh64.h"
 
 namespace gd {
@@ -442,6 +443,133 @@ __device__ uint32_t join_pair(const gpudiff_pair_row& r, uint32_t f, const uint8
     *noop = (((f & F_SPEC) && spec_weq) ? NOOP_SPEC : 0u) | (((f & F_STATUS) && stat_ok) ? NOOP_STATUS : 0u);
     if (f & F_SENT) {
         if (EMIT && lane == 0) {
+            out_h[base + n] = status_sentinel_hash((r.flags_a >> GPUDIFF_OBJ_SEED_SHIFT) & 0xFFu, mask);
+            out_k[base + n] = GPUDIFF_PATH_REGION_STATUS | GPUDIFF_PATH_STATUS_ABSENT;
+        }
+        n += 1;
+    }
+    return n;
+}
+
+// ---------------------------------------------------------------- K2: paths from the stream
+// K2's per-wave mismatch log (LDS): per pair of the item and region, how many chunks of the compare stream
+// mismatched and the first kSpLogCap of them (stream_paths.h: sp_entry).  A pair's slots are its own, so a
+// region whose tails shifted -- hundreds of mismatching chunks -- only runs its own count past the cap and
+// pushes nobody's entries out; a count past the cap sends that region to the merge-join.
+struct StreamLog {
+    uint32_t cnt[2][64];             // [status][pair]
+    uint32_t ent[2][64][kSpLogCap];  // sp_entry(the chunk's index in the item's stream, its differing dwords)
+    uint32_t first[64], n1[64];      // a pair's first chunk in the item's stream, its spec chunks
+};
+
+// The changed paths of a size-matched region from its c <= kSpLogCap logged chunks, by stream_paths.h's rule (a
+// lane per differing dword, then a lane per changed leaf): written where join_region<true> would write them, in
+// its order (ascending leaf = ascending key), with its *weq_all.  Returns the path count, or kSpRefuse with
+// nothing written that the join does not overwrite: the caller then joins the region.
+__device__ uint32_t stream_region(const RegionView& A, const RegionView& B, uint64_t seg, const uint32_t* ent,
+                                  uint32_t c, uint32_t g0, uint8_t region_bit, uint64_t* __restrict__ out_h,
+                                  uint8_t* __restrict__ out_k, uint32_t out_base, uint32_t lane, bool* weq_all) {
+    const uint32_t nc = 4u * c;  // <= 16 candidate lanes: dword (lane & 3) of entry (lane >> 2)
+    const uint32_t e = lane < nc ? ent[lane >> 2] - sp_entry(g0, 0u) : 0u;  // g0: the region's first chunk
+    const bool cand = lane < nc && ((sp_entry_dwords(e) >> (lane & 3u)) & 1u);
+    const uint64_t b = sp_entry_byte(e, lane & 3u);
+    const SpWhere w = sp_classify(b, A.L);
+    if (ballot(cand && (b >= seg || w.cls == SP_KEY))) return kSpRefuse;
+    uint32_t leaf = w.idx;
+    const bool ar = cand && w.cls == SP_ARENA;
+    if (ballot(ar)) {  // the owners of the arena dwords: the prefix sum of side A's tail sizes, 64 leaves a step
+        bool found = false;
+        uint32_t run = 0;
+        for (uint32_t i0 = 0; i0 < A.L; i0 += 64u) {
+            const uint32_t n = min(64u, A.L - i0);
+            const uint32_t as = lane < n ? meta_arena(A.metas[i0 + lane]) : 0u;
+            const uint32_t inc = wave_incl_scan(as);
+            const uint32_t tot = shfl32(inc, 63);
+            const uint32_t rel = w.idx - run;
+            uint32_t o = 0;  // window leaves whose tails end at or before the byte
+#pragma unroll
+            for (uint32_t s = 32; s >= 1; s >>= 1)
+                if (shfl32(inc, o + s - 1u) <= rel) o += s;
+            if (ar && !found && w.idx >= run && rel < tot) {  // then inc[o] > rel: o < n and its tail holds it
+                leaf = i0 + o;
+                found = true;
+            }
+            run += tot;
+            if (!ballot(ar && !found)) break;
+        }
+        if (ballot(ar && !found)) return kSpRefuse;  // the arena's final padding
+    }
+    // S: the distinct leaves, ranked ascending
+    bool dup = false;
+    for (uint32_t j = 0; j < nc; j++) {
+        const uint32_t xj = (uint32_t)__builtin_amdgcn_readlane((int)leaf, (int)j);
+        const bool cj = __builtin_amdgcn_readlane((int)(cand ? 1 : 0), (int)j) != 0;
+        if (cj && j < lane && xj == leaf) dup = true;
+    }
+    const bool uq = cand && !dup;
+    const uint64_t um = ballot(uq);
+    uint32_t rank = 0;
+    for (uint32_t j = 0; j < nc; j++) {
+        const uint32_t xj = (uint32_t)__builtin_amdgcn_readlane((int)leaf, (int)j);
+        if (((um >> j) & 1ull) && xj < leaf) rank++;
+    }
+    // one gather: the leaf's key and both sides' meta and val
+    uint32_t key = 0, ma = 0, mb = 0;
+    uint64_t xa = 0, xb = 0;
+    if (uq) {
+        key = A.keys[leaf];
+        ma = A.metas[leaf];
+        mb = B.metas[leaf];
+        xa = A.vals[leaf];
+        xb = B.vals[leaf];
+    }
+    if (ballot(uq && meta_arena(ma) != meta_arena(mb))) return kSpRefuse;  // a padded tail length changed
+    if (uq) {
+        out_h[out_base + rank] = key;
+        out_k[out_base + rank] = region_bit | GPUDIFF_PATH_CHANGED;
+    }
+    *weq_all = !ballot(uq && !wire_equal_number(ma, xa, mb, xb));
+    return popc64(um);
+}
+
+// join_pair<true> for K2's own pairs: a size-matched region the stream found dirty is emitted from the wave's
+// log when the rule allows (*n_stream counts those), joined otherwise; spec, status, sentinel as in join_pair
+__device__ uint32_t stream_pair(const gpudiff_pair_row& r, uint32_t f, const uint8_t* pool, uint64_t mask,
+                                uint64_t* out_h, uint8_t* out_k, uint32_t base, uint32_t lane, uint32_t* noop,
+                                const StreamLog* log, uint32_t k, bool log_ok, uint32_t* n_stream) {
+    uint32_t n = 0;
+    bool spec_weq = true, stat_weq = true;
+    if (f & F_JSPEC) {
+        RegionView A = region_view(pool, r.off_a, r.spec_l_a, r.spec_ar_a, false, r.spec_l_a);
+        RegionView B = region_view(pool, r.off_b, r.spec_l_b, r.spec_ar_b, false, r.spec_l_b);
+        const uint32_t c = log_ok ? uni(log->cnt[0][k]) : 0u;  // non-zero: the region was streamed (its sizes match)
+        const uint32_t g0 = uni(log->first[k]);
+        uint32_t got = kSpRefuse;
+        if (c >= 1u && c <= kSpLogCap)
+            got = stream_region(A, B, seg_bytes(r.spec_l_a, r.spec_ar_a), log->ent[0][k], c, g0, 0, out_h, out_k, base + n,
+                                lane, &spec_weq);
+        if (got == kSpRefuse) got = join_region<true>(A, B, 0, out_h, out_k, base + n, lane, &spec_weq);
+        else (*n_stream)++;
+        n += got;
+    }
+    if (f & F_JSTAT) {
+        RegionView A = region_view(pool, r.off_a, r.spec_l_a, r.spec_ar_a, true, r.stat_l_a);
+        RegionView B = region_view(pool, r.off_b, r.spec_l_b, r.spec_ar_b, true, r.stat_l_b);
+        const uint32_t c = log_ok ? uni(log->cnt[1][k]) : 0u;
+        const uint32_t g0 = uni(log->first[k]) + uni(log->n1[k]);
+        uint32_t got = kSpRefuse;
+        if (c >= 1u && c <= kSpLogCap)
+            got = stream_region(A, B, seg_bytes(r.stat_l_a, r.stat_ar_a), log->ent[1][k], c, g0,
+                                GPUDIFF_PATH_REGION_STATUS, out_h, out_k, base + n, lane, &stat_weq);
+        if (got == kSpRefuse)
+            got = join_region<true>(A, B, GPUDIFF_PATH_REGION_STATUS, out_h, out_k, base + n, lane, &stat_weq);
+        else (*n_stream)++;
+        n += got;
+    }
+    const bool stat_ok = stat_weq && (!(f & F_SENT) || !(r.flags_a & GPUDIFF_OBJ_HAS_STATUS));
+    *noop = (((f & F_SPEC) && spec_weq) ? NOOP_SPEC : 0u) | (((f & F_STATUS) && stat_ok) ? NOOP_STATUS : 0u);
+    if (f & F_SENT) {
+        if (lane == 0) {
             out_h[base + n] = status_sentinel_hash((r.flags_a >> GPUDIFF_OBJ_SEED_SHIFT) & 0xFFu, mask);
             out_k[base + n] = GPUDIFF_PATH_REGION_STATUS | GPUDIFF_PATH_STATUS_ABSENT;
         }
@@ -916,6 +1044,13 @@ __global__ __launch_bounds__(256, MINB) void k_compare_flat(const gpudiff_pair_r
         }
         __syncthreads();  // every slot initialised before a sibling reads it
     }
+    // the wave's mismatch log (the deep-pair kernel keeps the join: a helper's mismatches never reach the owner)
+    [[maybe_unused]] StreamLog* slog = nullptr;
+    [[maybe_unused]] uint32_t n_stream = 0;  // regions emitted from the stream (wave-uniform)
+    if constexpr (!HELP) {
+        __shared__ StreamLog stream_logs[4];
+        slog = &stream_logs[uni(threadIdx.x >> 6)];
+    }
     // one pass of a wave over chunks [base, base + 64 U) of an item's flattened stream (lane k's registers: pair k's
     // inclusive chunk prefix, first chunk, spec chunks, arena adjustments and blob offsets); mismatching chunks mark
     // their pairs in mis_s / mis_t
@@ -936,22 +1071,57 @@ __global__ __launch_bounds__(256, MINB) void k_compare_flat(const gpudiff_pair_r
             st[u] = k >= shfl32(n1, o);
             const uint32_t xa = shfl32(adj_a, o), xb = shfl32(adj_b, o);
             const uint64_t oa = shfl64(off_a, o), ob = shfl64(off_b, o);
-            own[u] = o;
+            own[u] = HELP ? o : o | (st[u] ? 64u : 0u);  // (the default kernel: the log's slot index)
             const uint64_t rel = 16ull * k;
             if (act[u]) {
                 va[u] = __builtin_nontemporal_load((const u32x4*)(pool + oa + rel + (st[u] ? xa : 0u)));
                 vb[u] = __builtin_nontemporal_load((const u32x4*)(pool + ob + rel + (st[u] ? xb : 0u)));
             }
         }
+        if constexpr (HELP) {
 #pragma unroll
-        for (int u = 0; u < U; u++) {
-            uint64_t m = ballot(act[u] && neq16(va[u], vb[u]));
-            while (m) {  // differing chunks: only in dirty pairs
-                const uint32_t j = (uint32_t)__builtin_ctzll(m);
-                m &= m - 1;
-                const uint64_t bit = 1ull << (uint32_t)__builtin_amdgcn_readlane((int)own[u], (int)j);
-                if (__builtin_amdgcn_readlane((int)(st[u] ? 1 : 0), (int)j)) mis_t |= bit;
-                else mis_s |= bit;
+            for (int u = 0; u < U; u++) {
+                uint64_t m = ballot(act[u] && neq16(va[u], vb[u]));
+                while (m) {  // differing chunks: only in dirty pairs
+                    const uint32_t j = (uint32_t)__builtin_ctzll(m);
+                    m &= m - 1;
+                    const uint64_t bit = 1ull << (uint32_t)__builtin_amdgcn_readlane((int)own[u], (int)j);
+                    if (__builtin_amdgcn_readlane((int)(st[u] ? 1 : 0), (int)j)) mis_t |= bit;
+                    else mis_s |= bit;
+                }
+            }
+        } else {
+            // each chunk pair reduced up front to one word -- owner | status << 6 | differing dwords << 7 (the
+            // compare's cost) -- so the 16 x U data registers are dead before the branches below
+            uint32_t info[U];
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                const uint32_t dw = (va[u].x != vb[u].x ? 1u : 0u) | (va[u].y != vb[u].y ? 2u : 0u) |
+                                    (va[u].z != vb[u].z ? 4u : 0u) | (va[u].w != vb[u].w ? 8u : 0u);
+                info[u] = own[u] | (act[u] ? dw << 7 : 0u);
+            }
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                const bool ne = info[u] >= 128u;
+                uint64_t m = ballot(ne);
+                // where each differing chunk lies, into its pair's slots of the wave's log (lane-parallel): its
+                // index in the item's stream (stream_pair makes it the index within the region), its differing dwords
+                if (m && ne) {
+                    const uint32_t q = info[u] & 127u;
+                    const uint32_t idx = __hip_atomic_fetch_add(&slog->cnt[0][0] + q, 1u, __ATOMIC_RELAXED,
+                                                                __HIP_MEMORY_SCOPE_WAVEFRONT);
+                    uint32_t l = lane;
+                    asm volatile("" : "+v"(l));  // recomputed here: not one more register per chunk kept since the loads
+                    if (idx < kSpLogCap)
+                        (&slog->ent[0][0][0])[q * kSpLogCap + idx] = sp_entry(base + (uint32_t)u * 64u + l, info[u] >> 7);
+                }
+                while (m) {  // differing chunks: only in dirty pairs
+                    const uint32_t j = (uint32_t)__builtin_ctzll(m);
+                    m &= m - 1;
+                    const uint32_t w = (uint32_t)__builtin_amdgcn_readlane((int)info[u], (int)j);
+                    if (w & 64u) mis_t |= 1ull << (w & 63u);
+                    else mis_s |= 1ull << (w & 63u);
+                }
             }
         }
     };
@@ -1095,6 +1265,10 @@ __global__ __launch_bounds__(256, MINB) void k_compare_flat(const gpudiff_pair_r
             mis_s = ((uint64_t)uni((uint32_t)(ms >> 32)) << 32) | uni((uint32_t)ms);
             mis_t = ((uint64_t)uni((uint32_t)(mt >> 32)) << 32) | uni((uint32_t)mt);
         } else {
+            slog->cnt[0][lane] = 0u;
+            slog->cnt[1][lane] = 0u;
+            slog->first[lane] = first;
+            slog->n1[lane] = n1;
             uint32_t pass = 0;
             for (uint32_t base = 0; base < total; base += 64u * U, pass++) {
                 stream_pass(base, total, incl, first, n1, adj_a, adj_b, off_a, off_b, mis_s, mis_t);
@@ -1153,7 +1327,8 @@ __global__ __launch_bounds__(256, MINB) void k_compare_flat(const gpudiff_pair_r
                     // per item 32 -> 15 us but raised K2 to 137 VGPRs, 3 waves/SIMD: config3 at 10M lost 3.5%,
                     // profiles/r06m, r06n; staging K3's whole deferrals cost K3 4.5 us a pass in LDS occupancy)
                     const gpudiff_pair_row r = rows[p0 + k];
-                    pc = join_pair<true>(r, fk, pool, mask, ah, ak, src, lane, &nb);
+                    if constexpr (HELP) pc = join_pair<true>(r, fk, pool, mask, ah, ak, src, lane, &nb);
+                    else pc = stream_pair(r, fk, pool, mask, ah, ak, src, lane, &nb, slog, k, total < (1u << 28), &n_stream);  // (a log entry holds 28 bits of chunk index)
                 } else if (fk & F_SENT) {  // status-absent only (every ConfigMap/Secret update)
                     const uint32_t fa = (uint32_t)__builtin_amdgcn_readlane((int)v3.x, (int)k);
                     nb = sentinel_noop_bits(fa);
@@ -1274,6 +1449,9 @@ __global__ __launch_bounds__(256, MINB) void k_compare_flat(const gpudiff_pair_r
         }
     }
     if (deferred && lane == 0) summary[6] = 1u;
+    if constexpr (!HELP) {
+        if (n_stream && lane == 0) atomicAdd(summary + 7, n_stream);
+    }
     if constexpr (PROF) {
         const uint64_t t_end = wall_clock64();
         if (lane == 0 && g_k2_prof && wave < g_k2_prof_cap) {

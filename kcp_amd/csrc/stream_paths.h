@@ -1,0 +1,102 @@
+// Changed paths of a size-matched dirty region straight from K2's stream: which leaf a
+// mismatching 16-B chunk of the compare stream belongs to, and when those leaves alone are the region's
+// changed paths, so that the merge-join (and its second read of the pair) is not needed.  Plain inline
+// arithmetic over the segment layout, shared by the kernel and the host test: no HIP runtime call.
+//
+// A segment is  vals[L] u64 | keys[L] u32 | metas[L] u32 | arena  (include/gpudiff_format.h); both sides of a
+// size-matched region have the same L and the same arena size, so byte b of the one is byte b of the other.
+//
+// The rule.  Let S be the leaves hit by a differing dword: a val or meta dword hits its leaf, an arena dword
+// the leaf whose tail [off(i), off(i) + meta_arena(m_i)) holds it (off = the prefix sum of meta_arena over side
+// A's metas).  The region qualifies when no key dword differs, every differing dword is placed, |S| <=
+// kSpMaxLeaves and meta_arena(ma_i) == meta_arena(mb_i) for every leaf of S.  Its changed paths are then exactly
+// the keys of S, all CHANGED: with equal L and equal (unique, ascending) keys the merge-join pairs leaf i with
+// leaf i and emits it iff its meta, val or tail differs; the leaves outside S have equal metas and those inside
+// equal padded tail lengths, so both sides' tails sit at equal offsets and a tail differs iff a differing arena
+// dword lies inside it.  Anything else -- a key dword, an arena dword no tail owns (the arena's final padding, the
+// stream's line padding), a tail whose padded length changed (every later tail shifts) -- goes to the join.
+#pragma once
+#include <stdint.h>
+
+#include "../../include/gpudiff_format.h"
+
+#if defined(__HIPCC__)
+#define GD_SP_HD __host__ __device__
+#else
+#define GD_SP_HD
+#endif
+
+namespace gd {
+
+constexpr uint32_t kSpLogCap = 4;        // mismatching chunks K2 logs per pair and region; one more: the join
+constexpr uint32_t kSpMaxLeaves = 64;    // |S| the emission handles (a lane per leaf)
+constexpr uint32_t kSpRefuse = 0xFFFFFFFFu;
+
+// a log entry: the chunk's index within its region and which of its four dwords differ
+GD_SP_HD inline uint32_t sp_entry(uint32_t chunk, uint32_t dwords) { return (chunk << 4) | (dwords & 15u); }
+GD_SP_HD inline uint32_t sp_entry_dwords(uint32_t e) { return e & 15u; }
+GD_SP_HD inline uint64_t sp_entry_byte(uint32_t e, uint32_t d) { return 16ull * (e >> 4) + 4u * d; }
+
+// arena bytes of a leaf's value: a long string's tail past its first 8 bytes, zero padded to 4
+GD_SP_HD inline uint32_t sp_meta_arena(uint32_t m) {
+    return ((m & 7u) == GPUDIFF_TAG_STR && (m >> 3) > GPUDIFF_INLINE_MAX) ? (((m >> 3) - GPUDIFF_INLINE_MAX + 3u) & ~3u)
+                                                                          : 0u;
+}
+
+enum SpClass : uint32_t { SP_VAL = 0, SP_KEY = 1, SP_META = 2, SP_ARENA = 3 };
+struct SpWhere {
+    uint32_t cls;
+    uint32_t idx;  // SP_VAL / SP_KEY / SP_META: the leaf; SP_ARENA: the byte's offset in the arena
+};
+// where the dword at byte b (a multiple of 4) of a region of L leaves lies.  L may be odd, so the boundaries
+// fall inside 16-B chunks: per dword, never per chunk
+GD_SP_HD inline SpWhere sp_classify(uint64_t b, uint32_t L) {
+    const uint64_t l = L;
+    if (b < 8u * l) return SpWhere{SP_VAL, (uint32_t)(b >> 3)};
+    if (b < 12u * l) return SpWhere{SP_KEY, (uint32_t)((b - 8u * l) >> 2)};
+    if (b < 16u * l) return SpWhere{SP_META, (uint32_t)((b - 12u * l) >> 2)};
+    return SpWhere{SP_ARENA, (uint32_t)(b - 16u * l)};
+}
+
+// the leaf whose tail holds arena byte ao; L when none does
+GD_SP_HD inline uint32_t sp_arena_owner(const uint32_t* metas, uint32_t L, uint32_t ao) {
+    uint32_t off = 0;
+    for (uint32_t i = 0; i < L; i++) {
+        const uint32_t n = sp_meta_arena(metas[i]);
+        if (ao - off < n) return i;  // off <= ao here
+        off += n;
+    }
+    return L;
+}
+
+// The whole rule, one region, serially (the kernel does the same a lane per differing dword): entries[n] are
+// the region's mismatching chunks, seg_a / seg_b its two sides of seg_bytes each.  Returns |S| with the leaves
+// ascending in leaves[], or kSpRefuse.
+GD_SP_HD inline uint32_t sp_region_rule(const uint8_t* seg_a, const uint8_t* seg_b, uint32_t L, uint64_t seg_bytes,
+                                        const uint32_t* entries, uint32_t n, uint32_t leaves[kSpMaxLeaves]) {
+    const uint32_t* ma = (const uint32_t*)(seg_a + 12ull * L);
+    const uint32_t* mb = (const uint32_t*)(seg_b + 12ull * L);
+    uint32_t ns = 0;
+    for (uint32_t q = 0; q < n; q++)
+        for (uint32_t d = 0; d < 4; d++) {
+            if (!((sp_entry_dwords(entries[q]) >> d) & 1u)) continue;
+            const uint64_t b = sp_entry_byte(entries[q], d);
+            if (b >= seg_bytes) return kSpRefuse;
+            const SpWhere w = sp_classify(b, L);
+            if (w.cls == SP_KEY) return kSpRefuse;
+            const uint32_t leaf = w.cls == SP_ARENA ? sp_arena_owner(ma, L, w.idx) : w.idx;
+            if (leaf >= L) return kSpRefuse;
+            uint32_t at = 0;  // sorted insert, once
+            while (at < ns && leaves[at] < leaf) at++;
+            if (at < ns && leaves[at] == leaf) continue;
+            if (ns == kSpMaxLeaves) return kSpRefuse;
+            for (uint32_t k = ns; k > at; k--) leaves[k] = leaves[k - 1];
+            leaves[at] = leaf;
+            ns++;
+        }
+    for (uint32_t k = 0; k < ns; k++)
+        if (sp_meta_arena(ma[leaves[k]]) != sp_meta_arena(mb[leaves[k]])) return kSpRefuse;
+    return ns;
+}
+
+}  // namespace gd
