@@ -560,6 +560,45 @@ int gpudiff_write_plan_get(gpudiff_ctx* ctx, gpudiff_ticket ticket, gpudiff_writ
 int gpudiff_write_plan_get_ex(gpudiff_ctx* ctx, gpudiff_ticket ticket, uint32_t mode, gpudiff_write_plan* out);
 void gpudiff_write_plan_release(gpudiff_ctx* ctx, gpudiff_write_plan* p);
 
+/* The write plan of a watch-replay batch: for a waited batch of a GPUDIFF_STORE_DEVICE_ENCODE
+ * store, ONE write per dirty slot, rendering the slot's LAST version of the batch -- the worker re-reads the
+ * latest object from the indexer and writes that (pkg/syncer/syncer.go:318), and the store is that indexer.  For
+ * every slot with at least one event in the batch and each kind K (spec, status):
+ *   dirty_K = OR over the slot's events in the batch of GPUDIFF_SPEC_DIRTY / GPUDIFF_STATUS_DIRTY (the final flags
+ *             gpudiff_wait returned, host-resolved events included);
+ *   if dirty_K, one write of kind K: the new_json of the slot's last event in the batch rendered as
+ *             GPUDIFF_UPSERT_SPEC / GPUDIFF_UPSERT_STATUS, pair_index = that event's index in the submitted array;
+ *   noop_K  = dirty_K and every event of the slot carrying the dirty bit of K also carries GPUDIFF_SPEC_NOOP /
+ *             GPUDIFF_STATUS_NOOP (a clean event leaves the region's wire bytes as they were, a no-op dirty event
+ *             too, so the last version's write carries what the write before the batch carried): no body.
+ * Spec writes ascending by pair_index, then status writes ascending.  An undecodable last version is listed with
+ * body status GPUDIFF_E_DECODE.  Several dirty events of one slot coalesce into one write (the reference would
+ * issue the same write once per event).  The plan of batch b is a function of batch b's events and flags alone: it
+ * does not look at batch b + 1, and it does not look at gpudiff_store_forget.
+ * mode: GPUDIFF_PLAN_SPEC / GPUDIFF_PLAN_STATUS select the kinds (neither = both);
+ * GPUDIFF_PLAN_UPSTREAM_DOWNSTREAM is GPUDIFF_E_INVAL (store events are informer events).
+ * The bodies come from the batch's JSON still staged in HBM: nothing is uploaded again, and only the bodies' bytes
+ * come back.  Call after gpudiff_wait on the ticket and before the submit after the next one (which reuses the ring
+ * slot); GPUDIFF_E_STATE otherwise, for an unknown or unwaited ticket, for a host-encode store (its JSON never
+ * reaches HBM) and for a store marked broken; GPUDIFF_E_CAPACITY when the plan's device buffers cannot be
+ * allocated.  Fills a gpudiff_write_plan; release with gpudiff_write_plan_release. */
+int gpudiff_store_write_plan_get(gpudiff_ctx* ctx, gpudiff_store* st, gpudiff_ticket ticket, uint32_t mode,
+                                 gpudiff_write_plan* out);
+/* What the store's last gpudiff_store_write_plan_get did (times with GPUDIFF_OPT_TIMING only, HIP events). */
+typedef struct gpudiff_store_plan_stats {
+    uint64_t calls;        /* plans built since the store was created */
+    uint64_t events, docs; /* the batch: events, staged documents */
+    uint64_t writes, noops, bodies, host_bodies;
+    uint64_t body_bytes;   /* bytes of the bodies K10 rendered */
+    uint64_t h2d_bytes;    /* uploaded: the host-resolved rows' flags, the deferred documents' gather list */
+    uint64_t d2h_bytes;    /* copied back: the two records, the write list, the bodies, the deferred documents' JSON */
+    uint64_t arena_bytes;  /* K10's output arena in HBM (never copied back) */
+    double fold_ms;        /* final flags + K17 + scans + K18 */
+    double k10_ms;
+    double pack_ms;        /* the lengths' scan + K19 */
+} gpudiff_store_plan_stats;
+int gpudiff_store_plan_stats_get(const gpudiff_store* st, gpudiff_store_plan_stats* out);
+
 /* The staged form: documents uploaded once into HBM (gpudiff_wbatch_create),
  * K10 launched on the context's stream (gpudiff_wbatch_run, asynchronous; with
  * GPUDIFF_OPT_TIMING each launch is bracketed by HIP events and

@@ -953,10 +953,15 @@ func (e *Engine) DiffAndPlanMode(olds, news [][]byte, mode uint32) ([]uint8, []W
 		return flags, nil, err
 	}
 	defer C.gpudiff_write_plan_release(e.ctx, &plan)
+	return flags, writesOf(&plan), nil
+}
+
+// writesOf copies a filled gpudiff_write_plan into Go memory (the caller releases the plan).
+func writesOf(plan *C.gpudiff_write_plan) []Write {
 	m := int(plan.n)
 	writes := make([]Write, m)
 	if m == 0 {
-		return flags, writes, nil
+		return writes
 	}
 	idx := (*[1 << 30]C.uint32_t)(unsafe.Pointer(plan.pair_index))[:m:m]
 	kind := (*[1 << 30]C.uint8_t)(unsafe.Pointer(plan.kind))[:m:m]
@@ -971,7 +976,24 @@ func (e *Engine) DiffAndPlanMode(olds, news [][]byte, mode uint32) ([]uint8, []W
 		}
 		writes[k] = w
 	}
-	return flags, writes, nil
+	return writes
+}
+
+// WritePlan lists the writes of one waited batch of a device-encode store (gpudiff_store_write_plan_get): one
+// write per dirty slot and kind, rendering the slot's LAST version of the batch from the JSON still staged in HBM
+// -- the worker re-reads the latest object from the indexer (syncer.go:318), and the store is that indexer.
+// Write.Pair is that event's index in the submitted batch.  mode: PlanSpec / PlanStatus select the kinds (0: both);
+// PlanUpstreamDownstream is refused (store events are informer events).  Call after the ticket was waited and
+// before the submit after the next one reuses its ring slot.
+func (s *Store) WritePlan(ticket uint64, mode uint32) ([]Write, error) {
+	s.e.mu.Lock()
+	defer s.e.mu.Unlock()
+	var plan C.gpudiff_write_plan
+	if err := errOf(C.gpudiff_store_write_plan_get(s.e.ctx, s.s, C.gpudiff_ticket(ticket), C.uint32_t(mode), &plan)); err != nil {
+		return nil, err
+	}
+	defer C.gpudiff_write_plan_release(s.e.ctx, &plan)
+	return writesOf(&plan), nil
 }
 
 // RollupGroup is the status roll-up of one root Deployment

@@ -33,6 +33,7 @@
 #include "dstore.h"
 #include "dstore_plan.h"
 #include "pathstr.h"
+#include "plan.h"
 
 #include <emmintrin.h>
 #include <string.h>
@@ -91,6 +92,30 @@ struct Ring {
     uint8_t* ps_out = nullptr;    // offsets[n + 1] | bytes: one D2H
     uint64_t ps_len_cap = 0, ps_tiles_cap = 0, ps_out_cap = 0;
     hipEvent_t ps_ev[4] = {};     // GPUDIFF_OPT_TIMING: K15 + scan begin/end, offsets + K16 begin/end
+    // gpudiff_store_write_plan_get (dstore_write_plan): what submit and wait keep for it -- the tables' extent and
+    // the host-resolved rows' final flags, nothing per event -- and its device buffers, cached and grown on demand
+    uint32_t nd = 0;              // staged documents of the batch (TokDoc[nd] at dmeta, DocLink[nd] at links_off)
+    uint64_t links_off = 0;
+    std::vector<PlanPatch> plan_patch;
+    uint8_t* pl_flags = nullptr;  // [nev] final flags
+    PlanPatch* pl_patch = nullptr;
+    uint8_t* pl_words = nullptr;  // [nd] K17's plan words
+    uint64_t* pl_tiles = nullptr;
+    uint64_t* pl_rec = nullptr;   // [16]: K17's totals, [8] the bodies' bytes
+    uint8_t* pl_head = nullptr;   // offsets | pair_index | src_doc | k10 | kind | noop: the write list as it goes back
+    uint32_t* pl_wdoc = nullptr;
+    uint64_t* pl_lens = nullptr;
+    TokDoc* pl_tdocs = nullptr;   // K10's table, its scratch, arena and results
+    TokOut* pl_touts = nullptr;
+    uint8_t* pl_scratch = nullptr;
+    uint8_t* pl_arena = nullptr;
+    uint8_t* pl_bytes = nullptr;  // K19's dense bodies
+    BlobMove* pl_mv = nullptr;    // K10's deferrals: the gather list and the gathered JSON
+    uint8_t* pl_gather = nullptr;
+    uint64_t pl_flags_cap = 0, pl_patch_cap = 0, pl_words_cap = 0, pl_tiles_cap = 0, pl_head_cap = 0, pl_wdoc_cap = 0,
+             pl_lens_cap = 0, pl_tdocs_cap = 0, pl_touts_cap = 0, pl_scratch_cap = 0, pl_arena_cap = 0,
+             pl_bytes_cap = 0, pl_mv_cap = 0, pl_gather_cap = 0;
+    hipEvent_t pl_ev[6] = {};     // GPUDIFF_OPT_TIMING: fold, K10, pack begin/end
 };
 
 // gpudiff_host_alloc's pinned buffers: a gpudiff_submit batch laid out in one of them (gpudiff.h) is uploaded
@@ -169,6 +194,7 @@ struct DStore {
     bool pair_mode = false;  // gpudiff_submit with GPUDIFF_OPT_DEVICE_ENCODE: slot i = pair i, no state kept
     gpudiff_store_stats st{};
     uint64_t deferred_total = 0;
+    gpudiff_store_plan_stats plan_st{};  // the last dstore_write_plan
     // GPUDIFF_OPT_TIMING: per-batch sums (ms) of host submit, H2D, K0, K0c+K0x
     double t_sum[4] = {0, 0, 0, 0};
     double t_sub[5] = {0, 0, 0, 0, 0};  // submit: slot wait, tables, copy, enqueue; finisher
@@ -673,6 +699,8 @@ int resolve(DStore* s, Ring& R, ResultStore& rs) {
     if (!fits && rc != GPUDIFF_E_CAPACITY) return rc;
     if ((rc = fits ? place_and_diff(s, W, ups, r2) : place_conservative(s, ups, W.drows.size()))) return rc;
     merge_results(R, W, rs, fits ? &r2 : nullptr, c->hash_mask);
+    // the write plan reads the batch's flags in HBM, where these rows are still the conservative ones K0x wrote
+    for (uint32_t row : W.drows) R.plan_patch.push_back(PlanPatch{row, rs.flags[row]});
     return GPUDIFF_OK;
 }
 
@@ -1202,6 +1230,7 @@ int finish_batch(DStore* s, Ring& R, ResultStore& rs) {
     }
     // the strings before resolve(): its compaction may pack into the space this batch's superseded blobs are in
     int rc = R.strs ? render_paths(s, R, rs) : GPUDIFF_OK;
+    R.plan_patch.clear();
     if (!rc && ndef) rc = resolve(s, R, rs);
     if (!rc && R.strs) {
         c->path_stats.paths += rs.ps.n;
@@ -1209,10 +1238,9 @@ int finish_batch(DStore* s, Ring& R, ResultStore& rs) {
         c->path_stats.host_paths += rs.ps.n_host;
     }
     if (rc) s->broken = true;
-    if (!rc && s->pair_mode) {  // kept for gpudiff_write_plan_get
+    if (!rc && s->pair_mode)  // kept for gpudiff_write_plan_get
         R.final_flags.assign(rs.flags.begin(), rs.flags.end());
-        R.waited = true;
-    }
+    if (!rc) R.waited = true;  // the ring slot holds a waited batch until its next submit (the write plans' window)
     // forgets older than every outstanding batch are settled
     for (auto it = s->forgotten.begin(); it != s->forgotten.end();)
         it = it->second < s->next_wait ? s->forgotten.erase(it) : std::next(it);
@@ -1235,6 +1263,7 @@ int dstore_submit(gpudiff_ctx* c, DStore* s, const gpudiff_event* ev, size_t n, 
     Ring* Rp = nullptr;
     if ((rc = claim_ring_slot(s, dec, &Rp))) return rc;
     Ring& R = *Rp;
+    R.waited = false;  // its tables are rewritten from here on: the previous batch's write plan is gone
     Lap lap{timing, s->t_sub};
     lap(0);
     const uint32_t batch = ++s->batch_seq;
@@ -1261,6 +1290,8 @@ int dstore_submit(gpudiff_ctx* c, DStore* s, const gpudiff_event* ev, size_t n, 
     R.waited = false;
     R.batch = batch;
     R.nev = (uint32_t)n;
+    R.nd = B.nd;
+    R.links_off = B.links_off();
     R.bound = B.bound;
     R.strs = strs;
     R.space_idx = s->cur;
@@ -1403,9 +1434,15 @@ void dstore_free(gpudiff_ctx* c, DStore* s) {
         if (R.d) gpudiff_dbatch_free(c, R.d);
         if (R.ticket) c->finishers.erase(R.ticket);
         for (void* p : {(void*)R.djson, (void*)R.dmeta, (void*)R.douts, (void*)R.dcoll, (void*)R.ddef, (void*)R.dcnt,
-                        (void*)R.dntab, (void*)R.ps_len, (void*)R.ps_tiles, (void*)R.ps_ctr, (void*)R.ps_out})
+                        (void*)R.dntab, (void*)R.ps_len, (void*)R.ps_tiles, (void*)R.ps_ctr, (void*)R.ps_out,
+                        (void*)R.pl_flags, (void*)R.pl_patch, (void*)R.pl_words, (void*)R.pl_tiles, (void*)R.pl_rec,
+                        (void*)R.pl_head, (void*)R.pl_wdoc, (void*)R.pl_lens, (void*)R.pl_tdocs, (void*)R.pl_touts,
+                        (void*)R.pl_scratch, (void*)R.pl_arena, (void*)R.pl_bytes, (void*)R.pl_mv,
+                        (void*)R.pl_gather})
             if (p) (void)hipFree(p);
         for (auto& e : R.ps_ev)
+            if (e) (void)hipEventDestroy(e);
+        for (auto& e : R.pl_ev)
             if (e) (void)hipEventDestroy(e);
         for (void* p : {(void*)R.hjson, (void*)R.hmeta})
             if (p) (void)hipHostFree(p);
@@ -1434,6 +1471,209 @@ void dstore_free(gpudiff_ctx* c, DStore* s) {
                     (void*)s->res_err})
         if (p) (void)hipFree(p);
     delete s;
+}
+
+// ------------------------------------------------------------------ the store's write plan
+namespace {
+
+// a plan buffer on the ring slot: kept across calls, grown (never per call) -- out of memory is the caller's
+// GPUDIFF_E_CAPACITY, not a device error
+template <class T>
+int grow_plan(T** p, uint64_t* cap, uint64_t need) {
+    if (need <= *cap) return GPUDIFF_OK;
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+    *cap = 0;
+    const uint64_t n = std::max<uint64_t>(need + need / 4, 64);
+    const hipError_t e = hipMalloc((void**)p, (size_t)n * sizeof(T));
+    if (e != hipSuccess) {
+        *p = nullptr;
+        (void)hipGetLastError();
+        gd::g_last_hip_error = hipGetErrorString(e);
+        return e == hipErrorOutOfMemory ? GPUDIFF_E_CAPACITY : GPUDIFF_E_DEVICE;
+    }
+    *cap = n;
+    return GPUDIFF_OK;
+}
+
+// the write list as K18 / K19 write it and one copy brings it back: 8-B words, then 4-B, then bytes
+struct PlanHead {
+    uint64_t off_pair, off_src, off_k10, off_kind, off_noop, bytes;
+    explicit PlanHead(uint64_t nw) {
+        off_pair = 8 * (nw + 1);
+        off_src = off_pair + 4 * nw;
+        off_k10 = off_src + 4 * nw;
+        off_kind = off_k10 + 4 * nw;
+        off_noop = off_kind + nw;
+        bytes = (off_noop + nw + 7) & ~7ull;
+    }
+};
+
+}  // namespace
+
+// The plan reads only what the waited batch left on its ring slot -- dmeta (documents, chains), djson, the diff
+// pass's flags on R.d -- and writes only the slot's pl_* buffers, so it runs on the readback stream: never behind
+// the other batch in flight on the kernel stream.  Its last read of djson / dmeta is marked in R.k0_done, which
+// the slot's next upload waits for (lifetimes).
+int dstore_write_plan(gpudiff_ctx* c, DStore* s, gpudiff_ticket t, uint32_t kinds, StorePlan* out) {
+    if (!s || s->broken || s->pair_mode || !t) return GPUDIFF_E_STATE;
+    Ring* Rp = nullptr;
+    for (Ring& Q : s->ring)
+        if (Q.ticket == t) Rp = &Q;
+    if (!Rp || !Rp->waited || Rp->outstanding) return GPUDIFF_E_STATE;  // unknown, not waited yet, or reused
+    Ring& R = *Rp;
+    hipStream_t st = c->rb;
+    const bool timing = (c->flags & GPUDIFF_OPT_TIMING) != 0;
+    if (timing && !R.pl_ev[0])
+        for (auto& e : R.pl_ev) HIPCHK(hipEventCreate(&e));
+    gpudiff_store_plan_stats S{};
+    S.calls = s->plan_st.calls + 1;
+    S.events = R.nev;
+    S.docs = R.nd;
+    int rc;
+    const uint32_t nev = R.nev, nd = R.nd, np = (uint32_t)R.plan_patch.size();
+    const uint32_t nt = plan_tiles(nd);
+    if ((rc = grow_plan(&R.pl_flags, &R.pl_flags_cap, nev)) || (rc = grow_plan(&R.pl_patch, &R.pl_patch_cap, np)) ||
+        (rc = grow_plan(&R.pl_words, &R.pl_words_cap, nd)) ||
+        (rc = grow_plan(&R.pl_tiles, &R.pl_tiles_cap, (uint64_t)kPlanCols * nt + 8)))
+        return rc;
+    if (!R.pl_rec) {
+        uint64_t cap = 0;
+        if ((rc = grow_plan(&R.pl_rec, &cap, 16))) return rc;
+    }
+    // 1. final flags, K17, the scan's top: the counts and byte totals
+    if (np) {
+        HIPCHK(hipMemcpyAsync(R.pl_patch, R.plan_patch.data(), np * sizeof(PlanPatch), hipMemcpyHostToDevice, st));
+        S.h2d_bytes += np * sizeof(PlanPatch);
+    }
+    if (timing) HIPCHK(hipEventRecord(R.pl_ev[0], st));
+    const gpudiff_dbatch* d = R.d;
+    HIPCHK(launch_plan_flags(st, d->flags, d->summary, d->dirty_idx, d->noop_d, R.pl_patch, np, nev, R.pl_flags));
+    const PlanIn in{(const TokDoc*)R.dmeta, (const DocLink*)(R.dmeta + R.links_off), nd, R.pl_flags, nev, kinds};
+    HIPCHK(launch_plan_tails(st, in, R.pl_words, R.pl_tiles, R.pl_rec));
+    uint64_t rec[kPlanCols] = {};
+    HIPCHK(hipMemcpyAsync(rec, R.pl_rec, sizeof(rec), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipEventRecord(R.k0_done, st));  // dmeta's read marker (no write: nothing after this reads it or djson)
+    R.k0_recorded = true;
+    HIPCHK(hipStreamSynchronize(st));
+    S.d2h_bytes += sizeof(rec);
+    const uint64_t nw = rec[kColSpecWrites] + rec[kColStatusWrites], n_sd = rec[kColSpecDocs],
+                   n_td = rec[kColStatusDocs], ndocs = n_sd + n_td;
+    if (nw > 2ull * nd || ndocs > nw) return GPUDIFF_E_DEVICE;  // not a scan of this table
+    out->n = (size_t)nw;
+    const PlanHead H(nw);
+    auto map_words = [&]() {
+        const uint8_t* b = (const uint8_t*)out->words.data();
+        out->offsets = out->words.data();
+        out->pair_index = (const uint32_t*)(b + H.off_pair);
+        out->src_doc = (const uint32_t*)(b + H.off_src);
+        out->k10 = (const int32_t*)(b + H.off_k10);
+        out->kind = b + H.off_kind;
+        out->noop = b + H.off_noop;
+        out->bytes = b + H.bytes;
+    };
+    if (!nw) {  // nothing to write: nothing more is launched
+        out->words.assign(1, 0);
+        map_words();
+        s->plan_st = S;
+        return GPUDIFF_OK;
+    }
+    // 2. K18 into the write list and K10's table, K10 once per kind, the bodies' lengths scanned
+    const uint64_t scratch_bytes = std::max(rec[kColSpecScratch], rec[kColStatusScratch]);
+    const uint64_t arena_bytes = rec[kColSpecCap] + rec[kColStatusCap];
+    if ((rc = grow_plan(&R.pl_head, &R.pl_head_cap, H.bytes)) || (rc = grow_plan(&R.pl_wdoc, &R.pl_wdoc_cap, nw)) ||
+        (rc = grow_plan(&R.pl_lens, &R.pl_lens_cap, nw)) || (rc = grow_plan(&R.pl_tdocs, &R.pl_tdocs_cap, ndocs)) ||
+        (rc = grow_plan(&R.pl_touts, &R.pl_touts_cap, ndocs)) ||
+        (rc = grow_plan(&R.pl_scratch, &R.pl_scratch_cap, scratch_bytes)) ||
+        (rc = grow_plan(&R.pl_arena, &R.pl_arena_cap, arena_bytes + 16)))  // K19 reads whole dwords
+        return rc;
+    const PlanLists L{(uint32_t*)(R.pl_head + H.off_pair), (uint32_t*)(R.pl_head + H.off_src), R.pl_wdoc,
+                      R.pl_head + H.off_kind, R.pl_head + H.off_noop, R.pl_tdocs, (uint32_t)nw, (uint32_t)ndocs};
+    HIPCHK(launch_plan_docs(st, in, R.pl_words, R.pl_tiles, R.pl_rec, L));
+    if (timing) HIPCHK(hipEventRecord(R.pl_ev[1], st));
+    if (timing) HIPCHK(hipEventRecord(R.pl_ev[2], st));
+    HIPCHK(launch_marshal_docs(st, R.pl_tdocs, (uint32_t)n_sd, R.djson, R.pl_scratch, R.pl_arena, GPUDIFF_UPSERT_SPEC,
+                               R.pl_touts));
+    HIPCHK(launch_marshal_docs(st, R.pl_tdocs + n_sd, (uint32_t)n_td, R.djson, R.pl_scratch, R.pl_arena,
+                               GPUDIFF_UPSERT_STATUS, R.pl_touts + n_sd));
+    HIPCHK(hipEventRecord(R.k0_done, st));  // the staged JSON's read marker, behind K10
+    if (timing) HIPCHK(hipEventRecord(R.pl_ev[3], st));
+    if (timing) HIPCHK(hipEventRecord(R.pl_ev[4], st));
+    HIPCHK(launch_body_lens(st, R.pl_wdoc, R.pl_touts, (uint32_t)nw, (uint32_t)ndocs, R.pl_lens,
+                            (int32_t*)(R.pl_head + H.off_k10), R.pl_tiles, R.pl_rec + 8));
+    uint64_t total = 0;
+    HIPCHK(hipMemcpyAsync(&total, R.pl_rec + 8, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    S.d2h_bytes += 8;
+    if (total > arena_bytes) return GPUDIFF_E_DEVICE;
+    // 3. K19: the bodies packed to their dense offsets; offsets | write list | bytes come back
+    if ((rc = grow_plan(&R.pl_bytes, &R.pl_bytes_cap, total + 8))) return rc;
+    HIPCHK(launch_pack_bodies(st, R.pl_wdoc, R.pl_touts, (uint32_t)nw, (uint32_t)ndocs, R.pl_lens, R.pl_tiles,
+                              (uint64_t*)R.pl_head, R.pl_arena, arena_bytes, R.pl_bytes, total));
+    if (timing) HIPCHK(hipEventRecord(R.pl_ev[5], st));
+    try {
+        out->words.assign((size_t)(H.bytes / 8 + (total + 7) / 8), 0);
+    } catch (const std::bad_alloc&) {
+        return GPUDIFF_E_NOMEM;
+    }
+    map_words();
+    HIPCHK(hipMemcpyAsync(out->words.data(), R.pl_head, H.bytes, hipMemcpyDeviceToHost, st));
+    if (total) HIPCHK(hipMemcpyAsync((uint8_t*)out->words.data() + H.bytes, R.pl_bytes, total, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    S.d2h_bytes += H.bytes + total;
+    if (out->offsets[nw] != total) return GPUDIFF_E_DEVICE;  // the offsets the bodies were packed by
+    // 4. K10's deferrals: their JSON gathered from djson on the device, one copy back (the caller's event buffers
+    //    are not read: they are only valid until gpudiff_wait)
+    const TokDoc* hdocs = (const TokDoc*)R.hmeta;
+    for (uint64_t w = 0; w < nw; w++) {
+        if (out->noop[w]) S.noops++;
+        else if (out->k10[w] != GPUDIFF_TOK_OK) out->def.push_back((uint32_t)w);
+    }
+    if (!out->def.empty()) {
+        const size_t n_def = out->def.size();
+        std::vector<BlobMove> mv(n_def);
+        out->hoff.resize(n_def);
+        out->hlen.resize(n_def);
+        uint64_t gb = 0;
+        for (size_t k = 0; k < n_def; k++) {
+            const uint32_t sd = out->src_doc[out->def[k]];
+            if (sd >= nd) return GPUDIFF_E_DEVICE;
+            // K7's 16-B copies: a staged document starts 16-B aligned and its span runs >= 16 B past its end
+            mv[k] = BlobMove{hdocs[sd].json_off, gb, ((uint64_t)hdocs[sd].json_len + 15u) & ~15ull};
+            out->hoff[k] = gb;
+            out->hlen[k] = hdocs[sd].json_len;
+            gb += mv[k].bytes;
+        }
+        if ((rc = grow_plan(&R.pl_mv, &R.pl_mv_cap, n_def)) || (rc = grow_plan(&R.pl_gather, &R.pl_gather_cap, gb + 16)))
+            return rc;
+        out->hjson.resize(gb);
+        HIPCHK(hipMemcpyAsync(R.pl_mv, mv.data(), n_def * sizeof(BlobMove), hipMemcpyHostToDevice, st));
+        HIPCHK(launch_move_blobs(st, R.djson, R.pl_gather, R.pl_mv, (uint32_t)n_def));
+        HIPCHK(hipEventRecord(R.k0_done, st));  // the read marker again, behind the last read of djson
+        if (gb) HIPCHK(hipMemcpyAsync(out->hjson.data(), R.pl_gather, gb, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        S.h2d_bytes += n_def * sizeof(BlobMove);
+        S.d2h_bytes += gb;
+    }
+    S.writes = nw;
+    S.bodies = ndocs;
+    S.host_bodies = out->def.size();
+    S.body_bytes = total;
+    S.arena_bytes = arena_bytes;
+    if (timing) {
+        float ms[3] = {0, 0, 0};
+        for (int k = 0; k < 3; k++) HIPCHK(hipEventElapsedTime(&ms[k], R.pl_ev[2 * k], R.pl_ev[2 * k + 1]));
+        S.fold_ms = ms[0];
+        S.k10_ms = ms[1];
+        S.pack_ms = ms[2];
+    }
+    s->plan_st = S;
+    return GPUDIFF_OK;
+}
+
+int dstore_plan_stats(const DStore* s, gpudiff_store_plan_stats* out) {
+    *out = s->plan_st;
+    return GPUDIFF_OK;
 }
 
 int dstore_staged_pairs(gpudiff_ctx* c, gpudiff_ticket t, StagedPairs* out) {

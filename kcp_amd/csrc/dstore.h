@@ -3,6 +3,8 @@
 #include "engine.h"
 #include "tokenize.h"
 
+#include <vector>
+
 struct DStore;
 
 DStore* dstore_create(gpudiff_ctx* c, uint32_t max_slots, uint64_t space_bytes, uint32_t max_events, int* rc);
@@ -32,3 +34,29 @@ struct StagedPairs {
 int dstore_staged_pairs(gpudiff_ctx* c, gpudiff_ticket t, StagedPairs* out);
 // work launched on the context stream now reads the batch's device JSON: the ring slot's next upload waits
 int dstore_staged_mark_read(gpudiff_ctx* c, gpudiff_ticket t);
+
+// ------------------------------------------------------------------ the store's write plan
+// gpudiff_store_write_plan_get's device side for a waited batch of a device-encode store: the write list and the
+// bodies K10 rendered, as they came back from the device in one allocation, and the JSON of the documents K10 left to
+// the host (gathered on the device, one copy back).  upsert.cpp marshals those and wraps the result.
+struct StorePlan {
+    size_t n = 0;                  // writes
+    std::vector<uint64_t> words;   // offsets[n + 1] | pair_index[n] | src_doc[n] | k10[n] | kind[n] | noop[n] | pad | bytes
+    const uint64_t* offsets = nullptr;    // dense: body w = bytes[offsets[w], offsets[w + 1]); empty unless K10 rendered it
+    const uint32_t* pair_index = nullptr;
+    const uint32_t* src_doc = nullptr;
+    const int32_t* k10 = nullptr;         // GPUDIFF_TOK_*; not OK: the host renders the body
+    const uint8_t* kind = nullptr;
+    const uint8_t* noop = nullptr;
+    const uint8_t* bytes = nullptr;
+    std::vector<uint32_t> def;     // the writes whose document K10 left to the host, ascending
+    std::vector<uint8_t> hjson;    // their documents' JSON: write def[k]'s at hjson[hoff[k]], hlen[k] bytes
+    std::vector<uint64_t> hoff;
+    std::vector<uint32_t> hlen;
+};
+// kinds: GPUDIFF_PLAN_SPEC | GPUDIFF_PLAN_STATUS.  GPUDIFF_E_STATE: not a waited ticket of this store whose ring slot
+// still holds the batch, or the store is broken; GPUDIFF_E_CAPACITY: no device memory for the plan's buffers
+int dstore_write_plan(gpudiff_ctx* c, DStore* s, gpudiff_ticket t, uint32_t kinds, StorePlan* out);
+int dstore_plan_stats(const DStore* s, gpudiff_store_plan_stats* out);
+// store.cpp: the device-encode store behind a gpudiff_store, null for a host-encode one
+DStore* gpudiff_store_dstore(gpudiff_store* s);

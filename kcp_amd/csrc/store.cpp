@@ -93,6 +93,8 @@ struct gpudiff_store {
     gpudiff_store_stats st{};
 };
 
+DStore* gpudiff_store_dstore(gpudiff_store* s) { return s ? s->dev : nullptr; }
+
 static int store_grow_moves(gpudiff_store* s, uint64_t n) {
     if (n <= s->moves_cap) return GPUDIFF_OK;
     if (s->moves_dev) (void)hipFree(s->moves_dev);

@@ -722,6 +722,76 @@ int gpudiff_write_plan_get_ex(gpudiff_ctx* c, gpudiff_ticket ticket, uint32_t mo
     return GPUDIFF_OK;
 }
 
+// The store's plan: the device lists the writes and renders the bodies (dstore_write_plan); what is
+// left here is the host path for the documents K10 deferred and wrapping the result.
+int gpudiff_store_write_plan_get(gpudiff_ctx* c, gpudiff_store* st, gpudiff_ticket ticket, uint32_t mode,
+                                 gpudiff_write_plan* out) {
+    if (!c || !st || !out) return GPUDIFF_E_INVAL;
+    // store events are informer events: there is no (A, B) reading of them
+    if (mode & ~(GPUDIFF_PLAN_SPEC | GPUDIFF_PLAN_STATUS)) return GPUDIFF_E_INVAL;
+    const uint32_t kinds = mode ? mode : (GPUDIFF_PLAN_SPEC | GPUDIFF_PLAN_STATUS);
+    memset(out, 0, sizeof(*out));
+    int rc = set_device(c);
+    if (rc) return rc;
+    DStore* ds = gpudiff_store_dstore(st);
+    if (!ds) return GPUDIFF_E_STATE;  // a host-encode store: its JSON never reaches HBM
+    StorePlan sp;
+    if ((rc = dstore_write_plan(c, ds, ticket, kinds, &sp))) return rc;
+    const size_t nw = sp.n, n_def = sp.def.size();
+    std::vector<std::string> hb(n_def);
+    std::vector<uint8_t> hok(n_def, 0);
+    if (n_def) {
+        const uint32_t T = std::max<uint32_t>(1, std::min<uint32_t>(c->threads, (uint32_t)((n_def + 63) / 64)));
+        auto work = [&](uint32_t t) {
+            for (size_t k = t; k < n_def; k += T)
+                hok[k] = host_body(sp.hjson.data() + sp.hoff[k], sp.hlen[k], sp.kind[sp.def[k]], hb[k]) ? 1 : 0;
+        };
+        workers(c).run(T, work);
+    }
+    std::unique_ptr<PlanStore> ps(new (std::nothrow) PlanStore());
+    std::unique_ptr<BodiesStore> bs(new (std::nothrow) BodiesStore());
+    if (!ps || !bs) return GPUDIFF_E_NOMEM;
+    ps->pair_index.assign(sp.pair_index, sp.pair_index + nw);
+    ps->kind.assign(sp.kind, sp.kind + nw);
+    ps->noop.assign(sp.noop, sp.noop + nw);
+    bs->status.assign(nw, 0);
+    bs->k10.assign(sp.k10, sp.k10 + nw);
+    bs->source.assign(nw, GPUDIFF_BODY_DEVICE);
+    if (!n_def) {  // the device's dense bodies are the result as they are
+        bs->offsets.assign(sp.offsets, sp.offsets + nw + 1);
+        bs->bytes.assign(sp.bytes, sp.bytes + sp.offsets[nw]);
+    } else {  // the host's bodies go in between
+        bs->offsets.resize(nw + 1);
+        size_t k = 0;
+        for (size_t w = 0; w < nw; w++) {
+            bs->offsets[w] = bs->bytes.size();
+            if (k < n_def && sp.def[k] == w) {
+                bs->source[w] = GPUDIFF_BODY_HOST;
+                if (hok[k]) bs->bytes.insert(bs->bytes.end(), hb[k].begin(), hb[k].end());
+                else bs->status[w] = GPUDIFF_E_DECODE;
+                k++;
+            } else {
+                bs->bytes.insert(bs->bytes.end(), sp.bytes + sp.offsets[w], sp.bytes + sp.offsets[w + 1]);
+            }
+        }
+        bs->offsets[nw] = bs->bytes.size();
+    }
+    publish(bs.release(), &out->bodies, nw, n_def);
+    out->n = nw;
+    out->pair_index = ps->pair_index.data();
+    out->kind = ps->kind.data();
+    out->noop = ps->noop.data();
+    out->internal = ps.release();
+    return GPUDIFF_OK;
+}
+
+int gpudiff_store_plan_stats_get(const gpudiff_store* st, gpudiff_store_plan_stats* out) {
+    if (!st || !out) return GPUDIFF_E_INVAL;
+    memset(out, 0, sizeof(*out));
+    DStore* ds = gpudiff_store_dstore(const_cast<gpudiff_store*>(st));
+    return ds ? dstore_plan_stats(ds, out) : GPUDIFF_E_STATE;
+}
+
 void gpudiff_write_plan_release(gpudiff_ctx* c, gpudiff_write_plan* p) {
     if (!p) return;
     gpudiff_bodies_release(c, &p->bodies);

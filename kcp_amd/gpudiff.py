@@ -223,6 +223,14 @@ class WritePlanC(C.Structure):
                 ("bodies", Bodies), ("internal", C.c_void_p)]
 
 
+class StorePlanStats(C.Structure):
+    _fields_ = [("calls", C.c_uint64), ("events", C.c_uint64), ("docs", C.c_uint64), ("writes", C.c_uint64),
+                ("noops", C.c_uint64), ("bodies", C.c_uint64), ("host_bodies", C.c_uint64),
+                ("body_bytes", C.c_uint64), ("h2d_bytes", C.c_uint64), ("d2h_bytes", C.c_uint64),
+                ("arena_bytes", C.c_uint64), ("fold_ms", C.c_double), ("k10_ms", C.c_double),
+                ("pack_ms", C.c_double)]
+
+
 class WBatchStats(C.Structure):
     _fields_ = [("n_docs", C.c_uint64), ("json_bytes", C.c_uint64), ("body_bytes", C.c_uint64),
                 ("scratch_bytes", C.c_uint64), ("out_cap_bytes", C.c_uint64), ("k10_ms", C.c_double),
@@ -351,6 +359,8 @@ SIGNATURES = [
     ("gpudiff_write_plan_get", C.c_int, [_P, C.c_uint64, C.POINTER(WritePlanC)]),
     ("gpudiff_write_plan_get_ex", C.c_int, [_P, C.c_uint64, C.c_uint32, C.POINTER(WritePlanC)]),
     ("gpudiff_write_plan_release", None, [_P, C.POINTER(WritePlanC)]),
+    ("gpudiff_store_write_plan_get", C.c_int, [_P, _P, C.c_uint64, C.c_uint32, C.POINTER(WritePlanC)]),
+    ("gpudiff_store_plan_stats_get", C.c_int, [_P, C.POINTER(StorePlanStats)]),
     ("gpudiff_wbatch_create", C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_size_t, C.c_uint32,
                                         C.POINTER(_P)]),
     ("gpudiff_wbatch_run", C.c_int, [_P, _P]),
@@ -618,6 +628,24 @@ class DeviceBatch:
             pass
 
 
+def _take_write_plan(ctx, wp: WritePlanC) -> "WritePlan":
+    """A filled gpudiff_write_plan as a WritePlan (copied), released."""
+    try:
+        n = wp.n
+        b = wp.bodies
+        offs = np.ctypeslib.as_array(C.cast(b.offsets, C.POINTER(C.c_uint64)), (n + 1,)).copy()
+        st = _arr(b.status, n, np.int32)
+        src = _arr(b.source, n, np.uint8)
+        total = int(offs[-1]) if n else 0
+        raw = C.string_at(b.bytes, total) if total else b""
+        return WritePlan(pair_index=_arr(wp.pair_index, n, np.uint32), kind=_arr(wp.kind, n, np.uint8),
+                         noop=_arr(wp.noop, n, np.uint8),
+                         bodies=[None if st[i] != OK else raw[int(offs[i]):int(offs[i + 1])] for i in range(n)],
+                         source=src, n_host=int(b.n_host))
+    finally:
+        _lib.gpudiff_write_plan_release(ctx, C.byref(wp))
+
+
 class ObjectStore:
     """Device-resident informer snapshot (gpudiff_store_*): submit(events)
     diffs each event's new object against its slot's resident version and
@@ -704,10 +732,26 @@ class ObjectStore:
         _chk(_lib.gpudiff_store_stats_get(self.h, C.byref(s)), "gpudiff_store_stats_get")
         return s
 
+    def write_plan(self, ticket: int, mode: int = PLAN_INFORMER) -> "WritePlan":
+        """gpudiff_store_write_plan_get: the writes of a waited batch of a device-encode store -- one per dirty
+        slot and kind, rendering the slot's last version of the batch from the JSON staged in HBM; pair_index is
+        that event's index in the submitted items.  mode: PLAN_SPEC / PLAN_STATUS select the kinds (neither: both)."""
+        wp = WritePlanC()
+        _chk(_lib.gpudiff_store_write_plan_get(self.engine.ctx, self.h, ticket, mode, C.byref(wp)),
+             "gpudiff_store_write_plan_get")
+        return _take_write_plan(self.engine.ctx, wp)
+
+    def plan_stats(self) -> StorePlanStats:
+        s = StorePlanStats()
+        _chk(_lib.gpudiff_store_plan_stats_get(self.h, C.byref(s)), "gpudiff_store_plan_stats_get")
+        return s
+
     def free(self):
-        if self.h:
+        if self.h and self.engine.ctx:
             _lib.gpudiff_store_free(self.engine.ctx, self.h)
-            self.h = C.c_void_p(0)
+        # (an engine closed first -- finalisers at interpreter exit run in any order -- took the context the store's
+        # teardown needs with it: the handle is dropped, not freed through a dead context)
+        self.h = C.c_void_p(0)
         for k in self._keep:
             if k is not None and isinstance(k[1], PinnedDocs):
                 k[1].free()
@@ -871,20 +915,7 @@ class Engine:
         | PLAN_SPEC / PLAN_STATUS: only those writes (neither: both)."""
         wp = WritePlanC()
         _chk(_lib.gpudiff_write_plan_get_ex(self.ctx, ticket, mode, C.byref(wp)), "gpudiff_write_plan_get_ex")
-        try:
-            n = wp.n
-            b = wp.bodies
-            offs = np.ctypeslib.as_array(C.cast(b.offsets, C.POINTER(C.c_uint64)), (n + 1,)).copy()
-            st = _arr(b.status, n, np.int32)
-            src = _arr(b.source, n, np.uint8)
-            total = int(offs[-1]) if n else 0
-            raw = C.string_at(b.bytes, total) if total else b""
-            return WritePlan(pair_index=_arr(wp.pair_index, n, np.uint32), kind=_arr(wp.kind, n, np.uint8),
-                             noop=_arr(wp.noop, n, np.uint8),
-                             bodies=[None if st[i] != OK else raw[int(offs[i]):int(offs[i + 1])] for i in range(n)],
-                             source=src, n_host=int(b.n_host))
-        finally:
-            _lib.gpudiff_write_plan_release(self.ctx, C.byref(wp))
+        return _take_write_plan(self.ctx, wp)
 
     def diff_pairs(self, pairs, ids=None, clusters=None) -> DiffResult:
         return self.wait(self.submit(pairs, ids, clusters))
