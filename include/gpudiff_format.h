@@ -42,6 +42,15 @@
 
 #include <stdint.h>
 
+/* The functions below are the format's arithmetic, written down once: the
+ * host, the oracle and the HIP kernels call them.  In a HIP translation unit
+ * they compile for both sides; in C and plain C++ the qualifier is empty. */
+#ifdef __HIPCC__
+#define GPUDIFF_HD __host__ __device__
+#else
+#define GPUDIFF_HD
+#endif
+
 #define GPUDIFF_TAG_NULL 0u
 #define GPUDIFF_TAG_FALSE 1u
 #define GPUDIFF_TAG_TRUE 2u
@@ -85,7 +94,7 @@
  * unique under the pair's seed): nothing agrees with it, so the next event on
  * its slot is re-encoded from old_json */
 #define GPUDIFF_TAB_NONE 0xFFFFFFFFu
-static inline uint64_t gpudiff_tab_bytes(uint32_t n, uint64_t key_bytes) {
+GPUDIFF_HD static inline uint64_t gpudiff_tab_bytes(uint32_t n, uint64_t key_bytes) {
     return (24ull * n + key_bytes + 127u) & ~(uint64_t)127u;  /* blobs stay GPUDIFF_BLOB_ALIGN multiples */
 }
 
@@ -110,12 +119,14 @@ typedef struct gpudiff_pair_row {
 } gpudiff_pair_row;
 
 /* segment bytes: 16 B per leaf record (a multiple of 16) + the arena */
-static inline uint64_t gpudiff_seg_bytes(uint32_t l, uint32_t arena) { return (uint64_t)l * 16u + (uint64_t)arena; }
+GPUDIFF_HD static inline uint64_t gpudiff_seg_bytes(uint32_t l, uint32_t arena) {
+    return (uint64_t)l * 16u + (uint64_t)arena;
+}
 
 #define GPUDIFF_BLOB_ALIGN 128u
 /* a blob's body: both segments, zero padded to GPUDIFF_BLOB_ALIGN -- the span the
  * decision kernel reads; a device-store blob's path table starts here */
-static inline uint64_t gpudiff_blob_body(uint32_t sl, uint32_t sar, uint32_t tl, uint32_t tar) {
+GPUDIFF_HD static inline uint64_t gpudiff_blob_body(uint32_t sl, uint32_t sar, uint32_t tl, uint32_t tar) {
     return (gpudiff_seg_bytes(sl, sar) + gpudiff_seg_bytes(tl, tar) + (GPUDIFF_BLOB_ALIGN - 1u)) &
            ~(uint64_t)(GPUDIFF_BLOB_ALIGN - 1u);
 }
@@ -125,7 +136,7 @@ static inline uint64_t gpudiff_blob_body(uint32_t sl, uint32_t sar, uint32_t tl,
  * and B has status; the spec segment when only the spec sizes match (padded to the line too when neither
  * side has status leaves); the status segment when only the status sizes match; nothing else (a size
  * mismatch decides the region without reading it).  The roofline's format bytes and the shard weight. */
-static inline uint64_t gpudiff_pair_compare_bytes(const gpudiff_pair_row* r) {
+GPUDIFF_HD static inline uint64_t gpudiff_pair_compare_bytes(const gpudiff_pair_row* r) {
     const uint64_t al = GPUDIFF_BLOB_ALIGN - 1u;
     uint64_t per = 0;
     if ((r->flags_a | r->flags_b) & GPUDIFF_OBJ_DECODE_ERR) return sizeof(gpudiff_pair_row) + 1u;
@@ -142,20 +153,20 @@ static inline uint64_t gpudiff_pair_compare_bytes(const gpudiff_pair_row* r) {
     return sizeof(gpudiff_pair_row) + 1u + 2u * per;
 }
 
-static inline uint32_t gpudiff_meta(uint32_t tag, uint32_t len) { return (len << 3) | tag; }
-static inline uint32_t gpudiff_meta_tag(uint32_t m) { return m & 7u; }
-static inline uint32_t gpudiff_meta_len(uint32_t m) { return m >> 3; }
-static inline int gpudiff_meta_is_long(uint32_t m) {
+GPUDIFF_HD static inline uint32_t gpudiff_meta(uint32_t tag, uint32_t len) { return (len << 3) | tag; }
+GPUDIFF_HD static inline uint32_t gpudiff_meta_tag(uint32_t m) { return m & 7u; }
+GPUDIFF_HD static inline uint32_t gpudiff_meta_len(uint32_t m) { return m >> 3; }
+GPUDIFF_HD static inline int gpudiff_meta_is_long(uint32_t m) {
     return gpudiff_meta_tag(m) == GPUDIFF_TAG_STR && gpudiff_meta_len(m) > GPUDIFF_INLINE_MAX;
 }
 /* arena bytes of one leaf's value (long strings: the tail past the 8 bytes in
  * vals, its length rounded up to 4) */
-static inline uint32_t gpudiff_meta_arena(uint32_t m) {
+GPUDIFF_HD static inline uint32_t gpudiff_meta_arena(uint32_t m) {
     return gpudiff_meta_is_long(m) ? ((gpudiff_meta_len(m) - GPUDIFF_INLINE_MAX + 3u) & ~3u) : 0u;
 }
 /* a segment's arena size (the row's *_ar fields): the sum of its leaves'
  * gpudiff_meta_arena, rounded up to 16 */
-static inline uint32_t gpudiff_arena_bytes(uint32_t sum) { return (sum + 15u) & ~15u; }
+GPUDIFF_HD static inline uint32_t gpudiff_arena_bytes(uint32_t sum) { return (sum + 15u) & ~15u; }
 
 #ifdef __cplusplus
 }

@@ -34,6 +34,7 @@
 #include "dstore_plan.h"
 #include "pathstr.h"
 #include "plan.h"
+#include "scan64.h"
 
 #include <emmintrin.h>
 #include <string.h>
@@ -290,7 +291,7 @@ int render_paths(DStore* s, Ring& R, ResultStore& rs) {
     if (ps.n > 0xFFFFFFFFull) return GPUDIFF_E_CAPACITY;
     int rc;
     const uint32_t n = (uint32_t)ps.n;
-    if ((rc = grow_dev(&R.ps_len, &R.ps_len_cap, n)) || (rc = grow_dev(&R.ps_tiles, &R.ps_tiles_cap, path_tiles(n) + 1)))
+    if ((rc = grow_dev(&R.ps_len, &R.ps_len_cap, n)) || (rc = grow_dev(&R.ps_tiles, &R.ps_tiles_cap, scan64_tiles(n) + 1)))
         return rc;
     if (!R.ps_ctr && (rc = dalloc(&R.ps_ctr, 2))) return rc;
     const bool timing = (c->flags & GPUDIFF_OPT_TIMING) != 0;
@@ -735,7 +736,7 @@ DStore* dstore_create(gpudiff_ctx* c, uint32_t max_slots, uint64_t space_bytes, 
     for (auto& sp : s->space)
         if ((rc = dalloc(&sp, s->space_bytes))) return fail(rc);
     if ((rc = dalloc(&s->used_base, 2)) || (rc = dalloc(&s->slots, max_slots)) || (rc = dalloc(&s->ctr, 4)) ||
-        (rc = dalloc(&s->sizes, max_slots)) || (rc = dalloc(&s->tile_sums, (max_slots + 1023) / 1024 + 1)) ||
+        (rc = dalloc(&s->sizes, max_slots)) || (rc = dalloc(&s->tile_sums, scan64_tiles(max_slots) + 1)) ||
         (rc = dalloc(&s->res_err, 1)))
         return fail(rc);
     s->used_dev = s->used_base;
@@ -1532,7 +1533,7 @@ int dstore_write_plan(gpudiff_ctx* c, DStore* s, gpudiff_ticket t, uint32_t kind
     S.docs = R.nd;
     int rc;
     const uint32_t nev = R.nev, nd = R.nd, np = (uint32_t)R.plan_patch.size();
-    const uint32_t nt = plan_tiles(nd);
+    const uint32_t nt = scan64_tiles(nd);
     if ((rc = grow_plan(&R.pl_flags, &R.pl_flags_cap, nev)) || (rc = grow_plan(&R.pl_patch, &R.pl_patch_cap, np)) ||
         (rc = grow_plan(&R.pl_words, &R.pl_words_cap, nd)) ||
         (rc = grow_plan(&R.pl_tiles, &R.pl_tiles_cap, (uint64_t)kPlanCols * nt + 8)))

@@ -15,13 +15,15 @@
 //                        and makes the last encoded version resident; with
 //                        GPUDIFF_OPT_PATH_STRINGS it also records each row's two
 //                        path-table entry counts for K15 / K16 (paths.hip)
-//   K8  k_slot_sizes / k_scan_* / k_pack_slots   compaction of the live blobs
-//                        into the other space
+//   K8  k_slot_sizes / scan64 / k_pack_slots   compaction of the live blobs
+//                        into the other space (the sizes' tile sums and total by
+//                        scan64.h, each tile's offsets inside k_pack_slots)
 //   K9  k_place          host-resolved blobs, rows and slot states
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/gpudiff.h"
+#include "scan64.h"
 #include "tokenize.h"
 
 namespace gd {
@@ -31,7 +33,6 @@ namespace {
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ uint32_t lane_id() { return __lane_id(); }
-__device__ __forceinline__ uint64_t seg_bytes(uint32_t l, uint32_t arena) { return (uint64_t)l * 16u + arena; }
 
 struct BlobRef {
     uint64_t off;
@@ -81,10 +82,10 @@ __global__ __launch_bounds__(256) void k_collide(const DocLink* __restrict__ lin
         // the path tables (include/gpudiff_format.h): a hash both hold must have the same parent
         // hash and the same last component in each
         const uint32_t na = A.ntab, nb = B.n_tab;
-        // each table at its blob's body end (gpudiff_blob_body: the segments rounded up to 128 B)
-        const uint64_t* ha = (const uint64_t*)(space + A.off + ((seg_bytes(A.sl, A.sar) + seg_bytes(A.tl, A.tar) + 127u) & ~127ull));
-        const uint64_t* hb = (const uint64_t*)(space + B.off + ((seg_bytes(B.spec_l, B.spec_ar) +
-                                                                 seg_bytes(B.stat_l, B.stat_ar) + 127u) & ~127ull));
+        // each table at its blob's body end
+        const uint64_t* ha = (const uint64_t*)(space + A.off + gpudiff_blob_body(A.sl, A.sar, A.tl, A.tar));
+        const uint64_t* hb =
+            (const uint64_t*)(space + B.off + gpudiff_blob_body(B.spec_l, B.spec_ar, B.stat_l, B.stat_ar));
         const uint8_t* ka = (const uint8_t*)(ha + 3ull * na);
         const uint8_t* kb = (const uint8_t*)(hb + 3ull * nb);
         for (uint32_t i = lane; i < nb; i += 64) {
@@ -217,60 +218,15 @@ __global__ __launch_bounds__(256) void k_slot_sizes(const DSlot* __restrict__ sl
     if (i < n) sizes[i] = (slots[i].flags & DS_LIVE) ? slots[i].bytes : 0ull;
 }
 
-// exclusive scan of u64 in tiles of 1024 (256 threads x 4): tile sums, then
-// a one-block scan of the tile sums, then each tile rescans with its base
-constexpr uint32_t kTile = 1024;
-
-__device__ uint64_t block_excl_scan(uint64_t v, uint64_t* tmp, uint64_t* total) {
-    const uint32_t t = threadIdx.x;
-    tmp[t] = v;
-    __syncthreads();
-    for (uint32_t d = 1; d < blockDim.x; d <<= 1) {
-        const uint64_t o = t >= d ? tmp[t - d] : 0ull;
-        __syncthreads();
-        tmp[t] += o;
-        __syncthreads();
-    }
-    const uint64_t incl = tmp[t];
-    *total = tmp[blockDim.x - 1];
-    __syncthreads();
-    return incl - v;
-}
-
-__global__ __launch_bounds__(256) void k_scan_tiles_u64(const uint64_t* __restrict__ in, uint32_t n,
-                                                        uint64_t* __restrict__ tile_sums) {
-    __shared__ uint64_t tmp[256];
-    const uint32_t base = blockIdx.x * kTile + threadIdx.x * 4;
-    uint64_t s = 0;
-    for (uint32_t k = 0; k < 4; k++)
-        if (base + k < n) s += in[base + k];
-    uint64_t total;
-    (void)block_excl_scan(s, tmp, &total);
-    if (threadIdx.x == 0) tile_sums[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(256) void k_scan_top_u64(uint64_t* __restrict__ tile_sums, uint32_t n_tiles,
-                                                      unsigned long long* __restrict__ used) {
-    __shared__ uint64_t tmp[256];
-    uint64_t run = 0;
-    for (uint32_t b = 0; b < n_tiles; b += 256) {
-        const uint32_t i = b + threadIdx.x;
-        const uint64_t v = i < n_tiles ? tile_sums[i] : 0ull;
-        uint64_t total;
-        const uint64_t ex = block_excl_scan(v, tmp, &total);
-        if (i < n_tiles) tile_sums[i] = run + ex;
-        run += total;
-    }
-    if (threadIdx.x == 0) *used = run;
-}
-
+// block per scan tile: the tile rescans its sizes on top of its base (tile_base: launch_scan64_sums' tile sums),
+// then copies its live blobs to their offsets
 __global__ __launch_bounds__(256) void k_pack_slots(DSlot* __restrict__ slots, uint32_t n,
                                                     const uint64_t* __restrict__ sizes,
                                                     const uint64_t* __restrict__ tile_base,
                                                     const uint8_t* __restrict__ src, uint8_t* __restrict__ dst) {
     __shared__ uint64_t tmp[256];
-    __shared__ uint64_t offs[kTile];
-    const uint32_t tile0 = blockIdx.x * kTile;
+    __shared__ uint64_t offs[kScanTile];
+    const uint32_t tile0 = blockIdx.x * kScanTile;
     const uint32_t base = tile0 + threadIdx.x * 4;
     uint64_t v[4], s = 0;
     for (uint32_t k = 0; k < 4; k++) {
@@ -278,7 +234,7 @@ __global__ __launch_bounds__(256) void k_pack_slots(DSlot* __restrict__ slots, u
         s += v[k];
     }
     uint64_t total;
-    uint64_t ex = block_excl_scan(s, tmp, &total) + tile_base[blockIdx.x];
+    uint64_t ex = block_excl_scan_u64(s, tmp, &total) + tile_base[blockIdx.x];
     for (uint32_t k = 0; k < 4; k++) {
         offs[threadIdx.x * 4 + k] = ex;
         ex += v[k];
@@ -286,7 +242,7 @@ __global__ __launch_bounds__(256) void k_pack_slots(DSlot* __restrict__ slots, u
     __syncthreads();
     // wave per live blob: 16-B copies
     const uint32_t lane = lane_id(), wave = threadIdx.x >> 6;
-    for (uint32_t j = wave; j < kTile; j += blockDim.x >> 6) {
+    for (uint32_t j = wave; j < kScanTile; j += blockDim.x >> 6) {
         const uint32_t i = tile0 + j;
         if (i >= n) break;
         const DSlot S = slots[i];
@@ -381,11 +337,10 @@ hipError_t launch_link(hipStream_t s, const uint32_t* heads, uint32_t n_heads, c
 
 hipError_t launch_compact_store(hipStream_t s, DSlot* slots, uint32_t n, const uint8_t* src, uint8_t* dst,
                                 uint64_t* sizes, uint64_t* block_sums, unsigned long long* used) {
-    const uint32_t tiles = (n + kTile - 1) / kTile;
     k_slot_sizes<<<(n + 255) / 256, 256, 0, s>>>(slots, n, sizes);
-    k_scan_tiles_u64<<<tiles, 256, 0, s>>>(sizes, n, block_sums);
-    k_scan_top_u64<<<1, 256, 0, s>>>(block_sums, tiles, used);
-    k_pack_slots<<<tiles, 256, 0, s>>>(slots, n, sizes, block_sums, src, dst);
+    const hipError_t e = launch_scan64_sums(s, sizes, n, block_sums, (uint64_t*)used);
+    if (e != hipSuccess) return e;
+    k_pack_slots<<<scan64_tiles(n), 256, 0, s>>>(slots, n, sizes, block_sums, src, dst);
     return hipGetLastError();
 }
 

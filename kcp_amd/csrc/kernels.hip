@@ -106,6 +106,7 @@ __device__ __forceinline__ uint32_t wave_max(uint32_t v) {
 }
 __device__ __forceinline__ uint32_t uni(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
 
+// must equal gpudiff_seg_bytes / gpudiff_meta_is_long / gpudiff_meta_arena (gpudiff_format.h); why restated: DESIGN.md §4j
 __device__ __forceinline__ uint64_t seg_bytes(uint32_t l, uint32_t arena) { return (uint64_t)l * 16u + arena; }
 __device__ __forceinline__ bool meta_long(uint32_t m) { return (m & 7u) == GPUDIFF_TAG_STR && (m >> 3) > 8u; }
 // arena bytes of a leaf's value: a long string's tail past its first 8 bytes (which sit in vals), at a

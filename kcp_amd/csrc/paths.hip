@@ -5,7 +5,7 @@
 //   K15 k_path_len    wave per dirty pair, lanes striding over the pair's changed-path entries: the table
 //                     by kind (CHANGED / ADDED: B's, REMOVED: A's; STATUS_ABSENT: the literal "status"), the
 //                     string's length, a counter of unresolved entries
-//   scan              exclusive u64 scan of the lengths in tiles of 1024 (dstore.hip's compaction scan)
+//   scan              exclusive u64 scan of the lengths (scan64.h: sums and total, then the offsets)
 //   K16 k_path_write  the same mapping; each string into its slot, packed back to back, no terminator
 //
 // Both kernels chase dependent loads (a binary search per step up the tree): latency-bound.  One pair's
@@ -15,24 +15,20 @@
 
 #include "../../include/gpudiff.h"
 #include "pathstr.h"
+#include "scan64.h"
 #include "tokenize.h"
 
 namespace gd {
 
 namespace {
 
-// gpudiff_blob_body (gpudiff_format.h is host C): both segments, rounded up to the 128-B line
-__device__ __forceinline__ uint64_t blob_body(uint32_t sl, uint32_t sar, uint32_t tl, uint32_t tar) {
-    return ((uint64_t)sl * 16u + sar + (uint64_t)tl * 16u + tar + 127u) & ~127ull;
-}
-
 // the table (and the root's hash) that renders entry kind `k` of row r; n = 0 when the side has none
 // or it does not lie inside the space
 __device__ __forceinline__ PathTab entry_tab(const PathJob& j, const gpudiff_pair_row& r, uint32_t row, uint32_t k) {
     const bool a = (k & 3u) == GPUDIFF_PATH_REMOVED;
     const uint64_t off = a ? r.off_a : r.off_b;
-    const uint64_t body = a ? blob_body(r.spec_l_a, r.spec_ar_a, r.stat_l_a, r.stat_ar_a)
-                            : blob_body(r.spec_l_b, r.spec_ar_b, r.stat_l_b, r.stat_ar_b);
+    const uint64_t body = a ? gpudiff_blob_body(r.spec_l_a, r.spec_ar_a, r.stat_l_a, r.stat_ar_a)
+                            : gpudiff_blob_body(r.spec_l_b, r.spec_ar_b, r.stat_l_b, r.stat_ar_b);
     const uint32_t n = j.ntab[2ull * row + (a ? 0u : 1u)];
     if (off > j.space_bytes || body > j.space_bytes - off) return path_tab(j.space, 0, 0);
     return path_tab(j.space + off + body, n, j.space_bytes - off - body);
@@ -99,69 +95,6 @@ __global__ __launch_bounds__(256) void k_path_write(const PathJob j, const uint6
     if (bad) atomicAdd(&ctr[1], (unsigned long long)bad);
 }
 
-// ---- exclusive u64 scan in tiles of kPathTile: tile sums, a one-block scan of them, each tile rescans
-__device__ uint64_t block_scan(uint64_t v, uint64_t* tmp, uint64_t* total) {
-    const uint32_t t = threadIdx.x;
-    tmp[t] = v;
-    __syncthreads();
-    for (uint32_t d = 1; d < blockDim.x; d <<= 1) {
-        const uint64_t o = t >= d ? tmp[t - d] : 0ull;
-        __syncthreads();
-        tmp[t] += o;
-        __syncthreads();
-    }
-    const uint64_t incl = tmp[t];
-    *total = tmp[blockDim.x - 1];
-    __syncthreads();
-    return incl - v;
-}
-
-__global__ __launch_bounds__(256) void k_path_tiles(const uint64_t* __restrict__ lens, uint32_t n,
-                                                    uint64_t* __restrict__ tile_sums) {
-    __shared__ uint64_t tmp[256];
-    const uint64_t base = (uint64_t)blockIdx.x * kPathTile + threadIdx.x * 4u;
-    uint64_t s = 0;
-    for (uint32_t k = 0; k < 4; k++)
-        if (base + k < n) s += lens[base + k];
-    uint64_t total;
-    (void)block_scan(s, tmp, &total);
-    if (threadIdx.x == 0) tile_sums[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(256) void k_path_top(uint64_t* __restrict__ tile_sums, uint32_t n_tiles,
-                                                  unsigned long long* __restrict__ ctr) {
-    __shared__ uint64_t tmp[256];
-    uint64_t run = 0;
-    for (uint32_t b = 0; b < n_tiles; b += 256) {
-        const uint32_t i = b + threadIdx.x;
-        const uint64_t v = i < n_tiles ? tile_sums[i] : 0ull;
-        uint64_t total;
-        const uint64_t ex = block_scan(v, tmp, &total);
-        if (i < n_tiles) tile_sums[i] = run + ex;
-        run += total;
-    }
-    if (threadIdx.x == 0) ctr[0] = run;
-}
-
-__global__ __launch_bounds__(256) void k_path_offsets(const uint64_t* __restrict__ lens, uint32_t n,
-                                                      const uint64_t* __restrict__ tile_sums,
-                                                      uint64_t* __restrict__ offsets) {
-    __shared__ uint64_t tmp[256];
-    const uint64_t base = (uint64_t)blockIdx.x * kPathTile + threadIdx.x * 4u;
-    uint64_t v[4], s = 0;
-    for (uint32_t k = 0; k < 4; k++) {
-        v[k] = base + k < n ? lens[base + k] : 0ull;
-        s += v[k];
-    }
-    uint64_t total;
-    uint64_t ex = block_scan(s, tmp, &total) + tile_sums[blockIdx.x];
-    for (uint32_t k = 0; k < 4; k++) {
-        if (base + k < n) offsets[base + k] = ex;
-        ex += v[k];
-        if (base + k + 1 == n) offsets[n] = ex;  // the end of the last string
-    }
-}
-
 }  // namespace
 
 hipError_t launch_path_len(hipStream_t s, const PathJob& j, uint64_t* lens, uint64_t* tile_sums,
@@ -171,16 +104,14 @@ hipError_t launch_path_len(hipStream_t s, const PathJob& j, uint64_t* lens, uint
     // an entry no dirty pair's range covers (none, by K6's CSR) would otherwise scan an unwritten length
     if ((e = hipMemsetAsync(lens, 0, 8ull * j.n_paths, s)) != hipSuccess) return e;
     k_path_len<<<(j.n_dirty + 3) / 4, 256, 0, s>>>(j, lens, ctr);
-    const uint32_t tiles = path_tiles(j.n_paths);
-    k_path_tiles<<<tiles, 256, 0, s>>>(lens, j.n_paths, tile_sums);
-    k_path_top<<<1, 256, 0, s>>>(tile_sums, tiles, ctr);
-    return hipGetLastError();
+    return launch_scan64_sums(s, lens, j.n_paths, tile_sums, (uint64_t*)ctr);  // ctr[0] = the total
 }
 
 hipError_t launch_path_write(hipStream_t s, const PathJob& j, const uint64_t* lens, const uint64_t* tile_sums,
                              uint64_t* offsets, uint8_t* bytes, uint64_t bytes_cap, unsigned long long* ctr) {
     if (!j.n_paths) return hipMemsetAsync(offsets, 0, 8, s);
-    k_path_offsets<<<path_tiles(j.n_paths), 256, 0, s>>>(lens, j.n_paths, tile_sums, offsets);
+    const hipError_t e = launch_scan64_offsets(s, lens, j.n_paths, tile_sums, offsets);
+    if (e != hipSuccess) return e;
     k_path_write<<<(j.n_dirty + 3) / 4, 256, 0, s>>>(j, offsets, bytes, bytes_cap, ctr);
     return hipGetLastError();
 }

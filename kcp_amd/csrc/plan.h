@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "scan64.h"
 #include "tokenize.h"
 
 namespace gd {
@@ -23,8 +24,8 @@ struct PlanPatch {
     uint32_t row, flags;
 };
 
-constexpr uint32_t kPlanTile = 1024;  // documents (K17 / K18) or writes (K19) per scan tile
-inline uint32_t plan_tiles(uint32_t n) { return (n + kPlanTile - 1) / kPlanTile; }
+constexpr uint32_t kPlanTile = 1024;  // K17 / K18's block: a lane per document, one scan tile per block
+static_assert(kPlanTile == kScanTile, "K17 / K18 write one row of tile sums per block");
 // the record the host sizes the buffers by (u64 each), and the columns of K17's tile sums
 enum PlanCol : uint32_t {
     kColSpecWrites = 0, kColStatusWrites, kColSpecDocs, kColStatusDocs,
@@ -49,7 +50,7 @@ constexpr uint32_t kPlanNoDoc = 0xFFFFFFFFu;
 hipError_t launch_plan_flags(hipStream_t s, const uint8_t* pass_flags, const uint32_t* summary,
                              const uint32_t* dirty_idx, const uint8_t* noop_d, const PlanPatch* patch,
                              uint32_t n_patch, uint32_t nev, uint8_t* flags);
-// K17 + the scan's first two steps: words[nd] (store_plan.h plan_word), tiles[plan_tiles(nd) * kPlanCols]
+// K17 + the scan's first two steps: words[nd] (store_plan.h plan_word), tiles[scan64_tiles(nd) * kPlanCols]
 // (exclusive, per column), rec[kPlanCols] = the totals
 hipError_t launch_plan_tails(hipStream_t s, const PlanIn& in, uint8_t* words, uint64_t* tiles, uint64_t* rec);
 // K18: the scan's last step and the compaction into `out`

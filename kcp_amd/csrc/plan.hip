@@ -9,10 +9,11 @@
 //                        event's plan word (which writes, which of them no-ops); per 64-document wave a ballot /
 //                        popcount of the writes by kind and of the ones with a body, per 1024-document tile their
 //                        sums and the sums of K10's scratch and arena room (u64)
-//   k_plan_top           one block: the tile sums' exclusive scans, the totals into the record the host reads
+//   scan64 top           one block: the tile sums' exclusive scans, column by column, and the totals into the
+//                        record the host reads (scan64.h launch_scan64_top over kPlanCols columns)
 //   K18 k_plan_docs      the same tile prefix again, plus the tile's base: each write into the write list, each body
 //                        into K10's TokDoc table -- document order is event order, so each kind comes out ascending
-//   k_body_lens / k_u64_tiles / k_u64_top / k_u64_offsets   K10's output sizes per write, scanned (u64)
+//   k_body_lens          K10's output sizes per write, then scanned (scan64.h: sums, top, offsets)
 //   K19 k_pack_bodies    wave per body: from its arena slot (2 x len + 512 B apart) to its byte-exact dense offset
 //
 // K19's copy works at dword granularity (store_plan.h plan_copy_body): a dense offset has any alignment, so each
@@ -28,6 +29,7 @@
 
 #include "../../include/gpudiff.h"
 #include "plan.h"
+#include "scan64.h"
 #include "store_plan.h"
 
 namespace gd {
@@ -60,23 +62,7 @@ __global__ __launch_bounds__(256) void k_plan_patch(const PlanPatch* __restrict_
     if (p.row < nev) flags[p.row] = (uint8_t)p.flags;
 }
 
-// ---------------------------------------------------------------- scans
-__device__ uint64_t block_scan(uint64_t v, uint64_t* tmp, uint64_t* total) {
-    const uint32_t t = threadIdx.x;
-    tmp[t] = v;
-    __syncthreads();
-    for (uint32_t d = 1; d < blockDim.x; d <<= 1) {
-        const uint64_t o = t >= d ? tmp[t - d] : 0ull;
-        __syncthreads();
-        tmp[t] += o;
-        __syncthreads();
-    }
-    const uint64_t incl = tmp[t];
-    *total = tmp[blockDim.x - 1];
-    __syncthreads();
-    return incl - v;
-}
-
+// ---------------------------------------------------------------- the tile's prefix
 // One tile of kPlanTile documents, a lane each (block of 1024 = 16 waves): this document's exclusive prefix inside
 // the tile and the tile's total, per column.  The four counts by ballot / popcount per wave and a sum over the
 // waves before it; the four byte sums by the block scan.
@@ -105,7 +91,7 @@ __device__ void tile_prefix(uint32_t w, uint32_t json_len, uint64_t pre[kPlanCol
     }
     const uint64_t scr = marshal_scratch_bytes(json_len), cap = marshal_out_cap(json_len);
     const uint64_t v[4] = {bit[2] ? scr : 0ull, bit[2] ? cap : 0ull, bit[3] ? scr : 0ull, bit[3] ? cap : 0ull};
-    for (uint32_t c = 0; c < 4; c++) pre[4 + c] = block_scan(v[c], tmp, &tot[4 + c]);
+    for (uint32_t c = 0; c < 4; c++) pre[4 + c] = block_excl_scan_u64(v[c], tmp, &tot[4 + c]);
 }
 
 // ---------------------------------------------------------------- K17
@@ -124,23 +110,6 @@ __global__ __launch_bounds__(kPlanTile) void k_plan_tails(const PlanIn in, uint8
     tile_prefix(w, len, pre, tot, tmp, wave_cnt);
     if (threadIdx.x == 0)
         for (uint32_t c = 0; c < kPlanCols; c++) tiles[(uint64_t)blockIdx.x * kPlanCols + c] = tot[c];
-}
-
-__global__ __launch_bounds__(256) void k_plan_top(uint64_t* __restrict__ tiles, uint32_t n_tiles,
-                                                  uint64_t* __restrict__ rec) {
-    __shared__ uint64_t tmp[256];
-    for (uint32_t c = 0; c < kPlanCols; c++) {
-        uint64_t run = 0;
-        for (uint32_t b = 0; b < n_tiles; b += 256) {
-            const uint32_t t = b + threadIdx.x;
-            const uint64_t v = t < n_tiles ? tiles[(uint64_t)t * kPlanCols + c] : 0ull;
-            uint64_t total;
-            const uint64_t ex = block_scan(v, tmp, &total);
-            if (t < n_tiles) tiles[(uint64_t)t * kPlanCols + c] = run + ex;
-            run += total;
-        }
-        if (threadIdx.x == 0) rec[c] = run;
-    }
 }
 
 // ---------------------------------------------------------------- K18
@@ -203,52 +172,6 @@ __global__ __launch_bounds__(256) void k_body_lens(const uint32_t* __restrict__ 
     k10[w] = st;
 }
 
-__global__ __launch_bounds__(256) void k_u64_tiles(const uint64_t* __restrict__ in, uint32_t n,
-                                                   uint64_t* __restrict__ tile_sums) {
-    __shared__ uint64_t tmp[256];
-    const uint64_t base = (uint64_t)blockIdx.x * kPlanTile + threadIdx.x * 4u;
-    uint64_t s = 0;
-    for (uint32_t k = 0; k < 4; k++)
-        if (base + k < n) s += in[base + k];
-    uint64_t total;
-    (void)block_scan(s, tmp, &total);
-    if (threadIdx.x == 0) tile_sums[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(256) void k_u64_top(uint64_t* __restrict__ tile_sums, uint32_t n_tiles,
-                                                 uint64_t* __restrict__ rec) {
-    __shared__ uint64_t tmp[256];
-    uint64_t run = 0;
-    for (uint32_t b = 0; b < n_tiles; b += 256) {
-        const uint32_t i = b + threadIdx.x;
-        const uint64_t v = i < n_tiles ? tile_sums[i] : 0ull;
-        uint64_t total;
-        const uint64_t ex = block_scan(v, tmp, &total);
-        if (i < n_tiles) tile_sums[i] = run + ex;
-        run += total;
-    }
-    if (threadIdx.x == 0) rec[0] = run;
-}
-
-__global__ __launch_bounds__(256) void k_u64_offsets(const uint64_t* __restrict__ in, uint32_t n,
-                                                     const uint64_t* __restrict__ tile_sums,
-                                                     uint64_t* __restrict__ offsets) {
-    __shared__ uint64_t tmp[256];
-    const uint64_t base = (uint64_t)blockIdx.x * kPlanTile + threadIdx.x * 4u;
-    uint64_t v[4], s = 0;
-    for (uint32_t k = 0; k < 4; k++) {
-        v[k] = base + k < n ? in[base + k] : 0ull;
-        s += v[k];
-    }
-    uint64_t total;
-    uint64_t ex = block_scan(s, tmp, &total) + tile_sums[blockIdx.x];
-    for (uint32_t k = 0; k < 4; k++) {
-        if (base + k < n) offsets[base + k] = ex;
-        ex += v[k];
-        if (base + k + 1 == n) offsets[n] = ex;  // the end of the last body
-    }
-}
-
 __global__ __launch_bounds__(256) void k_pack_bodies(const uint32_t* __restrict__ wdoc,
                                                      const TokOut* __restrict__ touts, uint32_t n_writes,
                                                      uint32_t n_docs, const uint64_t* __restrict__ offsets,
@@ -283,34 +206,31 @@ hipError_t launch_plan_flags(hipStream_t s, const uint8_t* pass_flags, const uin
 
 hipError_t launch_plan_tails(hipStream_t s, const PlanIn& in, uint8_t* words, uint64_t* tiles, uint64_t* rec) {
     if (!in.nd) return hipMemsetAsync(rec, 0, 8ull * kPlanCols, s);
-    const uint32_t nt = plan_tiles(in.nd);
+    const uint32_t nt = scan64_tiles(in.nd);
     k_plan_tails<<<nt, kPlanTile, 0, s>>>(in, words, tiles);
-    k_plan_top<<<1, 256, 0, s>>>(tiles, nt, rec);
-    return hipGetLastError();
+    return launch_scan64_top(s, tiles, nt, kPlanCols, rec);
 }
 
 hipError_t launch_plan_docs(hipStream_t s, const PlanIn& in, const uint8_t* words, const uint64_t* tiles,
                             const uint64_t* rec, const PlanLists& out) {
     if (!in.nd || !out.n_writes) return hipSuccess;
-    k_plan_docs<<<plan_tiles(in.nd), kPlanTile, 0, s>>>(in, words, tiles, rec, out);
+    k_plan_docs<<<scan64_tiles(in.nd), kPlanTile, 0, s>>>(in, words, tiles, rec, out);
     return hipGetLastError();
 }
 
 hipError_t launch_body_lens(hipStream_t s, const uint32_t* wdoc, const TokOut* touts, uint32_t n_writes,
                             uint32_t n_docs, uint64_t* lens, int32_t* k10, uint64_t* tiles, uint64_t* rec) {
     if (!n_writes) return hipMemsetAsync(rec, 0, 8, s);
-    const uint32_t nt = plan_tiles(n_writes);
     k_body_lens<<<(n_writes + 255) / 256, 256, 0, s>>>(wdoc, touts, n_writes, n_docs, lens, k10);
-    k_u64_tiles<<<nt, 256, 0, s>>>(lens, n_writes, tiles);
-    k_u64_top<<<1, 256, 0, s>>>(tiles, nt, rec);
-    return hipGetLastError();
+    return launch_scan64_sums(s, lens, n_writes, tiles, rec);
 }
 
 hipError_t launch_pack_bodies(hipStream_t s, const uint32_t* wdoc, const TokOut* touts, uint32_t n_writes,
                               uint32_t n_docs, const uint64_t* lens, const uint64_t* tiles, uint64_t* offsets,
                               const uint8_t* arena, uint64_t arena_bytes, uint8_t* bytes, uint64_t bytes_cap) {
     if (!n_writes) return hipMemsetAsync(offsets, 0, 8, s);
-    k_u64_offsets<<<plan_tiles(n_writes), 256, 0, s>>>(lens, n_writes, tiles, offsets);
+    const hipError_t e = launch_scan64_offsets(s, lens, n_writes, tiles, offsets);
+    if (e != hipSuccess) return e;
     k_pack_bodies<<<(n_writes + 3) / 4, 256, 0, s>>>(wdoc, touts, n_writes, n_docs, offsets, arena, arena_bytes, bytes,
                                                      bytes_cap);
     return hipGetLastError();

@@ -37,7 +37,8 @@ GD_SP_HD inline uint32_t sp_entry(uint32_t chunk, uint32_t dwords) { return (chu
 GD_SP_HD inline uint32_t sp_entry_dwords(uint32_t e) { return e & 15u; }
 GD_SP_HD inline uint64_t sp_entry_byte(uint32_t e, uint32_t d) { return 16ull * (e >> 4) + 4u * d; }
 
-// arena bytes of a leaf's value: a long string's tail past its first 8 bytes, zero padded to 4
+// arena bytes of a leaf's value: a long string's tail past its first 8 bytes, zero padded to 4; must equal
+// gpudiff_meta_arena (include/gpudiff_format.h), restated here because K2 compiles it
 GD_SP_HD inline uint32_t sp_meta_arena(uint32_t m) {
     return ((m & 7u) == GPUDIFF_TAG_STR && (m >> 3) > GPUDIFF_INLINE_MAX) ? (((m >> 3) - GPUDIFF_INLINE_MAX + 3u) & ~3u)
                                                                           : 0u;

@@ -279,6 +279,7 @@ __device__ __forceinline__ uint64_t hash_bytes(const uint8_t* p, uint32_t len) {
     return xxh64_words(0, len, [&](uint32_t i) -> uint64_t { return ld8u(p + 8u * i); });
 }
 
+// must equal gpudiff_seg_bytes / gpudiff_meta_arena (include/gpudiff_format.h); restated while K0's code stays as it is
 __device__ __forceinline__ uint64_t seg_bytes(uint32_t l, uint32_t arena) { return (uint64_t)l * 16u + arena; }
 __device__ __forceinline__ uint32_t meta_arena(uint32_t m) {
     // long strings: the tail past the first 8 bytes, at a 4-byte aligned arena offset (include/gpudiff_format.h)

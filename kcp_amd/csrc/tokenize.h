@@ -273,10 +273,8 @@ struct PathJob {
     uint64_t mask;              // the context's path-hash mask (the root's hash is seed & mask)
     uint32_t n_dirty, n_paths;
 };
-constexpr uint32_t kPathTile = 1024;  // the scan's tile (256 threads x 4)
-inline uint32_t path_tiles(uint32_t n_paths) { return (n_paths + kPathTile - 1) / kPathTile; }
-// K15 k_path_len + the scan's first two steps: lens[n_paths], tile_sums[path_tiles] (exclusive), ctr[0] = the
-// strings' total bytes; ctr[1] (zeroed here) counts unresolved entries
+// K15 k_path_len + the scan's first two steps (scan64.h): lens[n_paths], tile_sums[scan64_tiles(n_paths)]
+// (exclusive), ctr[0] = the strings' total bytes; ctr[1] (zeroed here) counts unresolved entries
 hipError_t launch_path_len(hipStream_t s, const PathJob& j, uint64_t* lens, uint64_t* tile_sums,
                            unsigned long long* ctr);
 // the scan's last step (offsets[n_paths + 1]) + K16 k_path_write: string i at bytes[offsets[i], offsets[i + 1])

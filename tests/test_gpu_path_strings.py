@@ -4,6 +4,7 @@ strings ride with the result (gpudiff_result_path_strings).  Every comparison is
 golden fixtures' third column or the oracle's render_path, in result order."""
 import copy
 import ctypes as C
+import functools
 import json
 import random
 
@@ -15,7 +16,7 @@ from oracle import gpudiff_oracle as O
 from tests import path_strings_cases as PC
 from tests.golden import fixtures as F
 from tests.golden.kat_cases import cases as kat_cases
-from tests.parity import assert_matches
+from tests.parity import assert_matches, oracle_batch
 from tests.workload import _noise, configmap, crd, deployment, mutate
 
 pytestmark = pytest.mark.gpu
@@ -237,7 +238,52 @@ def test_non_ascii_keys():
     eng.close()
 
 
-# ---------------------------------------------------------------- 7. option off
+# ---------------------------------------------------------------- 7. path counts at the scan's edges
+_EDGE_MAX = 2049
+
+
+def _one_path_pair(i):
+    """A ConfigMap-style pair whose one changed path is data.key-<i> (its status is there and unchanged, so no
+    `status` sentinel joins it); the key's and the names' lengths vary, so no two neighbouring offsets repeat."""
+    a = {"apiVersion": "v1", "kind": "ConfigMap", "metadata": {"name": "cm-%d" % i},
+         "data": {"key-%d" % i: "a" * (i % 13)}, "status": {"ok": True}}
+    b = copy.deepcopy(a)
+    b["data"]["key-%d" % i] += "x"
+    return G.to_json_bytes(a), G.to_json_bytes(b)
+
+
+@functools.lru_cache(maxsize=None)
+def _edge_pairs():
+    """The pairs and the oracle's results, computed once for every case below (a case takes a prefix)."""
+    pairs = [_one_path_pair(i) for i in range(_EDGE_MAX)]
+    return pairs, oracle_batch(pairs)
+
+
+@pytest.mark.parametrize("n", [1, 1023, 1024, 1025, _EDGE_MAX])
+def test_path_counts_at_scan_edges(n):
+    """n strings with n at the scan tile's edges (scan64: tiles of 1024): one value, a tile less one, a whole tile, a
+    tile and one, two tiles and one."""
+    pairs, exp = _edge_pairs()
+    pairs, exp = pairs[:n], exp[:n]
+    eng = G.Engine(device=0, encode_threads=4, flags=ON)
+    res = eng.wait(eng.submit(pairs))
+    _check_strings(res, assert_matches(res, pairs, exp=exp))
+    assert len(res.path_strings) == n and res.paths_host == 0
+    assert res.path_strings[n - 1] == b"data.key-%d" % (n - 1)
+    eng.close()
+
+
+def test_no_dirty_pair_has_no_strings():
+    """No changed path: nothing to scan, an empty list comes back (not None: the option is on)."""
+    pairs = [(_one_path_pair(i)[0],) * 2 for i in range(5)]
+    eng = G.Engine(device=0, encode_threads=2, flags=ON)
+    res = eng.wait(eng.submit(pairs))
+    _check_strings(res, assert_matches(res, pairs))
+    assert len(res.dirty_ids) == 0 and len(res.path_strings) == 0
+    eng.close()
+
+
+# ---------------------------------------------------------------- 8. option off
 def _raw_wait(eng, ticket):
     r = G.Result()
     assert G.lib().gpudiff_wait(eng.ctx, ticket, C.byref(r)) == G.OK

@@ -113,6 +113,25 @@ def test_compaction_keeps_results_exact(dev):
     e.close()
 
 
+def test_compaction_scan_crosses_every_tile_edge():
+    """The compaction's u64 scan (scan64) runs over max_slots sizes.  256 * 1024 + 1025 slots are 258 tiles of 1024:
+    the one-block scan of the tile sums takes its second trip (more than 256 tiles), and the last tile holds one
+    slot.  Live objects sit only on the two slots before and behind each edge -- the first tile's, the first trip's,
+    the array's -- so every blob's new offset depends on a base carried across one of them."""
+    max_slots = 256 * 1024 + 1025
+    slots = [0, 1023, 1024, 1025, 262143, 262144, 262145, max_slots - 1]
+    stream = [([(slots[s], nj, oj) for s, nj, oj in evs], pairs) for evs, pairs in _stream(11, len(slots), 16, 24)]
+    e = G.Engine(device=0, encode_threads=4)
+    st = e.object_store(max_slots=max_slots, space_bytes=256 << 10, max_events=64, device_encode=True)
+    _run(e, st, stream)
+    s = st.stats()
+    assert s.compactions >= 2, s.compactions
+    assert s.events == 16 * 24 and s.live_slots == len(slots)
+    assert s.used_bytes <= 256 << 10
+    st.free()
+    e.close()
+
+
 @MODES
 def test_compaction_keeps_path_tables(dev):
     """Blobs moved by compactions keep their path tables whole: with room for
