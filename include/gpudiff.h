@@ -110,8 +110,19 @@ enum {
                                                 gpudiff_store_submit on a GPUDIFF_STORE_DEVICE_ENCODE store): kernels
                                                 K15 / K16 render every changed path as text inside gpudiff_wait
                                                 (gpudiff_result_path_strings) */
-#define GPUDIFF_OPT_KNOWN \
-    (GPUDIFF_OPT_TIMING | (0xFu << GPUDIFF_OPT_ARENA_SHIFT) | GPUDIFF_OPT_DEVICE_ENCODE | GPUDIFF_OPT_PATH_STRINGS)
+#define GPUDIFF_OPT_SMALL_PASS 0x20000000u   /* a diff pass of 1..GPUDIFF_SMALL_PASS_MAX_PAIRS pairs runs as ONE kernel
+                                                (K20: decision, joins, compaction and path copy fused) and comes back
+                                                in one read-back; results are those of the ordinary pass, byte for
+                                                byte (gpudiff_pass_stats_get) */
+#define GPUDIFF_OPT_KNOWN                                                                                         \
+    (GPUDIFF_OPT_TIMING | (0xFu << GPUDIFF_OPT_ARENA_SHIFT) | GPUDIFF_OPT_DEVICE_ENCODE | GPUDIFF_OPT_PATH_STRINGS | \
+     GPUDIFF_OPT_SMALL_PASS)
+
+/* GPUDIFF_OPT_SMALL_PASS: the largest pass the fused kernel takes (64 chunks of 64 pairs: its finishing block scans
+ * the chunks with one lane each), and the most changed paths it finishes itself -- a pass with more is run again as
+ * the ordinary pass inside gpudiff_wait (gpudiff_pass_stats.redo_paths) */
+#define GPUDIFF_SMALL_PASS_MAX_PAIRS 4096u
+#define GPUDIFF_SMALL_PASS_MAX_PATHS 32768u
 
 #define GPUDIFF_DEVICE_CURRENT (-1)
 #define GPUDIFF_DEVICE_NONE (-2)   /* host-only context: encoding only */
@@ -327,6 +338,21 @@ void gpudiff_result_release(gpudiff_ctx* ctx, gpudiff_result* res);
 int gpudiff_last_timings(gpudiff_ctx* ctx, gpudiff_timings* t);
 int gpudiff_timing_reset(gpudiff_ctx* ctx);
 int gpudiff_sync(gpudiff_ctx* ctx);
+/* What the context's diff passes cost since gpudiff_open (GPUDIFF_OPT_SMALL_PASS).  A pass takes the fused kernel
+ * iff the option is set, 1 <= n_pairs <= GPUDIFF_SMALL_PASS_MAX_PAIRS, no gather send buffer is bound
+ * (gpudiff_dbatch_bind_gather) and no gpudiff_k2_profile buffer is installed; every other pass is the ordinary one.
+ * The kernel declines to finish a pass whose paths do not fit the batch's path arena (redo_arena), that holds a join
+ * over more keys than one wave takes (redo_deep: the ordinary pass slices those over many waves) or that has more
+ * than GPUDIFF_SMALL_PASS_MAX_PATHS changed paths (redo_paths); gpudiff_wait then runs the ordinary pass over the
+ * batch.  GPUDIFF_E_NODEVICE on a host-only context. */
+typedef struct gpudiff_pass_stats {
+    uint64_t passes;          /* diff passes enqueued */
+    uint64_t small_passes;    /* fused small passes launched */
+    uint64_t small_redone;    /* of those: declined by the kernel, run again as the ordinary pass in gpudiff_wait */
+    uint64_t redo_arena, redo_deep, redo_paths; /* small_redone by reason (a pass can count under several) */
+    uint64_t readback_rounds; /* host synchronisations spent reading results back, over all passes */
+} gpudiff_pass_stats;
+int gpudiff_pass_stats_get(gpudiff_ctx* ctx, gpudiff_pass_stats* out);
 
 /* encode + upload into a context-owned batch + diff (the syncer batcher's call) */
 int gpudiff_submit(gpudiff_ctx* ctx, const gpudiff_json_pair* pairs, size_t n,

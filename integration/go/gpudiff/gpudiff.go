@@ -883,6 +883,10 @@ func (e *Engine) UpsertBodies(objs []interface{}, mode Mode) ([][]byte, error) {
 // OptDeviceEncode opens an engine whose submits send raw JSON to the GPU (kernel K0); DiffAndPlan needs it.
 const OptDeviceEncode = uint32(C.GPUDIFF_OPT_DEVICE_ENCODE)
 
+// OptSmallPass: a flush of at most GPUDIFF_SMALL_PASS_MAX_PAIRS events runs as one kernel (K20) and comes back in
+// one read-back; results are the ordinary pass's.  A Batcher with a short flush window wants it.
+const OptSmallPass = uint32(C.GPUDIFF_OPT_SMALL_PASS)
+
 // Write is one API call the syncer's decisions imply (gpudiff_write_plan_get_ex).  For informer
 // pairs (PlanInformer) both kinds render the NEW object -- UpdateFunc enqueues newObj
 // (specsyncer.go:47-50, statussyncer.go:32-35) and the worker writes it: a spec write is

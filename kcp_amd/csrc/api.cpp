@@ -20,6 +20,7 @@
 #include "dstore.h"
 #include "engine.h"
 #include "kernels.h"
+#include "small_pass.h"
 #include "xxh64.h"
 
 using namespace gd;
@@ -206,6 +207,7 @@ void gpudiff_close(gpudiff_ctx* c) {
             (void)hipStreamSynchronize(c->rb);
             (void)hipStreamDestroy(c->rb);
         }
+        if (c->small_rb) (void)hipHostFree(c->small_rb);
         if (c->own_stream) (void)hipStreamDestroy(c->stream);
     }
     delete c;
@@ -667,6 +669,58 @@ static int enqueue_join_emit(gpudiff_ctx* c, gpudiff_dbatch* d) {
     return GPUDIFF_OK;
 }
 
+// The ordinary pass over n_pairs > 0 pairs: K2 .. K6 on the context stream, ev[1..4] after its phases
+static int enqueue_ordinary_pass(gpudiff_ctx* c, gpudiff_dbatch* d, const DiffBuffers& b, hipEvent_t* ev) {
+    hipStream_t ms = c->stream;
+    uint4* total = (uint4*)d->summary;  // summary[0..3]: n_spec, n_status, n_dirty, scratch cap
+    const uint32_t nchunks = (uint32_t)((d->n_pairs + 63) / 64);
+    HIPCHK(launch_compare(ms, b));  // zeroes the summary (+ K2's item counters) first
+    if (ev) HIPCHK(hipEventRecord(ev[1], ms));
+    HIPCHK(launch_compact(ms, b, 0, nchunks, nullptr, total));
+    if (ev) HIPCHK(hipEventRecord(ev[2], ms));
+    HIPCHK(launch_join(ms, b, 0, nchunks, nullptr, total));
+    if (ev) HIPCHK(hipEventRecord(ev[3], ms));
+    HIPCHK(launch_emit(ms, b));
+    if (ev) HIPCHK(hipEventRecord(ev[4], ms));
+    return GPUDIFF_OK;
+}
+
+// GPUDIFF_OPT_SMALL_PASS: which passes the fused kernel K20 takes (include/gpudiff.h, gpudiff_pass_stats)
+static bool takes_small_pass(const gpudiff_ctx* c, const gpudiff_dbatch* d) {
+    return (c->flags & GPUDIFF_OPT_SMALL_PASS) && d->n_pairs >= 1 && d->n_pairs <= GPUDIFF_SMALL_PASS_MAX_PAIRS &&
+           !d->gather_send && !c->k2_timeline;
+}
+
+// a device or pinned allocation of the small pass: out of memory is a capacity error (the caller can fall back to
+// a context without the option), anything else a device error
+static int small_alloc_rc(hipError_t e) {
+    if (e == hipSuccess) return GPUDIFF_OK;
+    if (e == hipErrorOutOfMemory) {
+        (void)hipGetLastError();
+        return GPUDIFF_E_CAPACITY;
+    }
+    g_last_hip_error = hipGetErrorString(e);
+    return GPUDIFF_E_DEVICE;
+}
+
+// K20: one memset and one launch; the whole kernel lies between ev[0] and ev[1], so compare_ms carries it
+static int enqueue_small_pass(gpudiff_ctx* c, gpudiff_dbatch* d, const DiffBuffers& b, hipEvent_t* ev) {
+    int rc;
+    if (!d->small_image && (rc = small_alloc_rc(hipMalloc((void**)&d->small_image, small_image_capacity()))))
+        return rc;
+    if (!c->small_rb &&
+        (rc = small_alloc_rc(hipHostMalloc((void**)&c->small_rb, small_image_capacity(), hipHostMallocDefault))))
+        return rc;
+    hipStream_t ms = c->stream;
+    const uint64_t arena = d->arena_cap >> ((c->flags >> GPUDIFF_OPT_ARENA_SHIFT) & 0xFu);  // the test hook shrinks it
+    HIPCHK(launch_small_pass(ms, b, arena, d->small_image));
+    if (ev)
+        for (int i = 1; i < 5; i++) HIPCHK(hipEventRecord(ev[i], ms));
+    d->small_pending = true;
+    c->pass_stats.small_passes++;
+    return GPUDIFF_OK;
+}
+
 int gpudiff_diff(gpudiff_ctx* c, gpudiff_dbatch* d, gpudiff_ticket* ticket) {
     if (!c || !d) return GPUDIFF_E_INVAL;
     int rc = set_device(c);
@@ -704,21 +758,16 @@ int gpudiff_diff(gpudiff_ctx* c, gpudiff_dbatch* d, gpudiff_ticket* ticket) {
         for (const gpudiff_dbatch* v : fam->views) shared = shared || busy(v);
         b.k2_shared = shared ? 1u : 0u;
     }
-    uint4* total = (uint4*)d->summary;  // summary[0..3]: n_spec, n_status, n_dirty, scratch cap
     if (ev) HIPCHK(hipEventRecord(ev[0], ms));
+    c->pass_stats.passes++;
+    d->small_pending = false;
     if (d->n_pairs == 0) {
         HIPCHK(hipMemsetAsync(d->summary, 0, kSummaryWords * sizeof(uint32_t), ms));
         HIPCHK(hipMemsetAsync(d->path_off, 0, sizeof(uint32_t), ms));
+    } else if (takes_small_pass(c, d)) {
+        if ((rc = enqueue_small_pass(c, d, b, ev))) return rc;
     } else {
-        const uint32_t nchunks = (uint32_t)((d->n_pairs + 63) / 64);
-        HIPCHK(launch_compare(ms, b));  // zeroes the summary (+ K2's item counters) first
-        if (ev) HIPCHK(hipEventRecord(ev[1], ms));
-        HIPCHK(launch_compact(ms, b, 0, nchunks, nullptr, total));
-        if (ev) HIPCHK(hipEventRecord(ev[2], ms));
-        HIPCHK(launch_join(ms, b, 0, nchunks, nullptr, total));
-        if (ev) HIPCHK(hipEventRecord(ev[3], ms));
-        HIPCHK(launch_emit(ms, b));
-        if (ev) HIPCHK(hipEventRecord(ev[4], ms));
+        if ((rc = enqueue_ordinary_pass(c, d, b, ev))) return rc;
     }
     if (ev) c->n_pass++;
     HIPCHK(hipEventRecord(d->done, c->stream));
@@ -775,6 +824,14 @@ int gpudiff_last_timings(gpudiff_ctx* c, gpudiff_timings* t) {
     return GPUDIFF_OK;
 }
 
+int gpudiff_pass_stats_get(gpudiff_ctx* c, gpudiff_pass_stats* out) {
+    if (!c || !out) return GPUDIFF_E_INVAL;
+    memset(out, 0, sizeof(*out));
+    if (!c->has_device) return GPUDIFF_E_NODEVICE;
+    *out = c->pass_stats;
+    return GPUDIFF_OK;
+}
+
 int gpudiff_wait(gpudiff_ctx* c, gpudiff_ticket ticket, gpudiff_result* res) {
     if (!c || !res) return GPUDIFF_E_INVAL;
     memset(res, 0, sizeof(*res));
@@ -810,16 +867,84 @@ int gpudiff_wait(gpudiff_ctx* c, gpudiff_ticket ticket, gpudiff_result* res) {
 
 }  // extern "C"
 
+// the write-path no-op bits of the dirty pairs (K2 / K4 via K3, or K20) onto the public flag bits
+static void apply_noop_bits(ResultStore* rs, const std::vector<uint32_t>& idx, const std::vector<uint8_t>& nb) {
+    for (uint8_t& f : rs->flags) f &= (uint8_t)(GPUDIFF_SPEC_DIRTY | GPUDIFF_STATUS_DIRTY | GPUDIFF_DECODE_ERROR);
+    for (size_t k = 0; k < idx.size(); k++) {
+        uint8_t& f = rs->flags[idx[k]];
+        if (f & GPUDIFF_DECODE_ERROR) continue;
+        if ((nb[k] & 1u) && (f & GPUDIFF_SPEC_DIRTY)) f |= GPUDIFF_SPEC_NOOP;
+        if ((nb[k] & 2u) && (f & GPUDIFF_STATUS_DIRTY)) f |= GPUDIFF_STATUS_NOOP;
+    }
+}
+
+// A finished small pass: the result image's first-round prefix in one copy into the context's pinned buffer and
+// one synchronisation; a second copy of the remainder only when the image is longer than the prefix.
+// *declined: K20 did not finish the pass (the reasons are counted): the caller runs the ordinary pass.
+static int collect_small(gpudiff_ctx* c, gpudiff_dbatch* d, ResultStore* rs, bool* declined) {
+    *declined = false;
+    hipStream_t rb = c->rb;
+    const uint64_t cap = small_image_capacity();
+    const uint64_t first = std::min<uint64_t>(
+        small_first_round_bytes((uint32_t)std::min<uint64_t>(d->n_pairs, GPUDIFF_SMALL_PASS_MAX_PAIRS)), cap);
+    HIPCHK(hipMemcpyAsync(c->small_rb, d->small_image, first, hipMemcpyDeviceToHost, rb));
+    HIPCHK(hipStreamSynchronize(rb));
+    c->pass_stats.readback_rounds++;
+    std::vector<uint32_t> idx;
+    std::vector<uint8_t> nb;
+    uint64_t need = 0;
+    uint32_t reason = 0;
+    try {
+        SmallUnpack u = small_unpack(c->small_rb, first, cap, *rs, idx, nb, &need, &reason);
+        if (u == SMALL_MORE && need > first && need <= cap) {
+            HIPCHK(hipMemcpyAsync(c->small_rb + first, d->small_image + first, need - first, hipMemcpyDeviceToHost, rb));
+            HIPCHK(hipStreamSynchronize(rb));
+            c->pass_stats.readback_rounds++;
+            u = small_unpack(c->small_rb, need, cap, *rs, idx, nb, &need, &reason);
+        }
+        if (u == SMALL_DECLINED) {
+            c->pass_stats.small_redone++;
+            if (reason & kSmallArena) c->pass_stats.redo_arena++;
+            if (reason & kSmallDeep) c->pass_stats.redo_deep++;
+            if (reason & kSmallPaths) c->pass_stats.redo_paths++;
+            *declined = true;
+            return GPUDIFF_OK;
+        }
+        if (u != SMALL_OK) {
+            g_last_hip_error = "small pass: malformed result image";
+            return GPUDIFF_E_DEVICE;
+        }
+    } catch (const std::bad_alloc&) {
+        return GPUDIFF_E_NOMEM;
+    }
+    apply_noop_bits(rs, idx, nb);
+    return GPUDIFF_OK;
+}
+
 int collect_results(gpudiff_ctx* c, gpudiff_dbatch* d, ResultStore& rsr) {
     ResultStore* rs = &rsr;
     int rc;
     HIPCHK(hipEventSynchronize(d->done));
+    if (d->small_pending) {
+        bool declined = false;
+        if ((rc = collect_small(c, d, rs, &declined))) return rc;
+        if (!declined) return GPUDIFF_OK;
+        // K20 declined: the ordinary pass over the same batch, behind whatever the stream holds by now.  Its rows
+        // and pool are the batch's until the next diff of it replaces this ticket (as for the scratch-overflow
+        // re-run below); `done` then stands for this pass.
+        DiffBuffers b = buffers_of(c, d);
+        if ((rc = enqueue_ordinary_pass(c, d, b, nullptr))) return rc;
+        HIPCHK(hipEventRecord(d->done, c->stream));
+        HIPCHK(hipEventSynchronize(d->done));
+        d->small_pending = false;
+    }
     // read back on the context's readback stream: a synchronous hipMemcpy would also wait for the
     // work queued behind this batch (the next batch's K0 / diff pass), serialising the pipeline
     hipStream_t rb = c->rb;
     uint32_t sum[8];
     HIPCHK(hipMemcpyAsync(sum, d->summary, sizeof(sum), hipMemcpyDeviceToHost, rb));
     HIPCHK(hipStreamSynchronize(rb));
+    c->pass_stats.readback_rounds++;
     if (sum[4]) {  // path scratch overflow: grow to the exact need and redo the join
         if ((rc = ensure_paths(d, d->arena_cap, sum[3]))) return rc;
         uint32_t zero = 0;
@@ -828,6 +953,7 @@ int collect_results(gpudiff_ctx* c, gpudiff_dbatch* d, ResultStore& rsr) {
         HIPCHK(hipStreamSynchronize(c->stream));
         HIPCHK(hipMemcpyAsync(sum, d->summary, sizeof(sum), hipMemcpyDeviceToHost, rb));
         HIPCHK(hipStreamSynchronize(rb));
+        c->pass_stats.readback_rounds++;
         if (sum[4]) return GPUDIFF_E_CAPACITY;
     }
     std::vector<uint32_t> idx;
@@ -858,13 +984,8 @@ int collect_results(gpudiff_ctx* c, gpudiff_dbatch* d, ResultStore& rsr) {
     HIPCHK(d2h(rs->hashes.data(), d->out_h, sum[5] * 8ull));
     HIPCHK(d2h(rs->kinds.data(), d->out_k, sum[5]));
     HIPCHK(hipStreamSynchronize(rb));
-    for (uint8_t& f : rs->flags) f &= (uint8_t)(GPUDIFF_SPEC_DIRTY | GPUDIFF_STATUS_DIRTY | GPUDIFF_DECODE_ERROR);
-    for (uint32_t k = 0; k < sum[2]; k++) {  // the write-path no-op bits of the dirty pairs (K2 / K4 via K3)
-        uint8_t& f = rs->flags[idx[k]];
-        if (f & GPUDIFF_DECODE_ERROR) continue;
-        if ((nb[k] & 1u) && (f & GPUDIFF_SPEC_DIRTY)) f |= GPUDIFF_SPEC_NOOP;
-        if ((nb[k] & 2u) && (f & GPUDIFF_STATUS_DIRTY)) f |= GPUDIFF_STATUS_NOOP;
-    }
+    c->pass_stats.readback_rounds++;
+    apply_noop_bits(rs, idx, nb);
     return GPUDIFF_OK;
 }
 

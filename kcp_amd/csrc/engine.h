@@ -116,6 +116,10 @@ struct gpudiff_dbatch {
     uint32_t* tail_perm = nullptr;  // K2's largest-first final round (kernels.h DiffBuffers)
     gd::TailPermKey tail_perm_key;
     uint64_t rows_gen = 0;  // bumped whenever the rows change (appends, resets, store batches): K2's cached order
+    // GPUDIFF_OPT_SMALL_PASS: the result image K20 packs (small_pass.h; allocated by the batch's first small pass),
+    // and whether the pass `done` stands for was a small one (collect_results reads the image then)
+    uint8_t* small_image = nullptr;
+    bool small_pending = false;
 };
 
 struct DStore;
@@ -175,6 +179,8 @@ struct gpudiff_ctx {
     std::vector<std::array<hipEvent_t, 5>> pass_ev;
     size_t n_pass = 0;
     hipStream_t rb = nullptr;     // result readback (never behind work queued after the batch)
+    gpudiff_pass_stats pass_stats{};  // gpudiff_pass_stats_get
+    uint8_t* small_rb = nullptr;  // GPUDIFF_OPT_SMALL_PASS: pinned read-back buffer of one result image (first use)
     // per-ticket completion hooks run by gpudiff_wait before results are
     // published (the device-encode store resolves its host-deferred events)
     std::unordered_map<gpudiff_ticket, std::function<int(ResultStore&)>> finishers;
@@ -216,7 +222,8 @@ inline void dfree_all(gpudiff_dbatch* d) {
                   d->status_ids, d->dirty_ids, d->dirty_idx, d->scratch_off, d->path_count, d->path_off,
                   d->tile_sums, d->path_src, d->path_cnt, d->arena_h, d->arena_k,
                   d->scratch_h, d->scratch_k, d->out_h, d->out_k, d->nbits, d->noop_d, d->slot_owner,
-                  d->slice_cnt, d->slice_weq, d->ids_alt[0], d->ids_alt[1], d->summary_alt, d->tail_perm};
+                  d->slice_cnt, d->slice_weq, d->ids_alt[0], d->ids_alt[1], d->summary_alt, d->tail_perm,
+                  d->small_image};
     for (void* p : ps)
         if (p) (void)hipFree(p);
     if (d->done) (void)hipEventDestroy(d->done);

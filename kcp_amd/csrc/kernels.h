@@ -98,6 +98,11 @@ hipError_t launch_slot_owners(hipStream_t s, const DiffBuffers& b);
 hipError_t launch_join(hipStream_t s, const DiffBuffers& b, uint32_t c0, uint32_t c1, const uint4* before,
                        const uint4* after);
 hipError_t launch_emit(hipStream_t s, const DiffBuffers& b);
+// K20 (smallpass.hip): the whole pass over 1..GPUDIFF_SMALL_PASS_MAX_PAIRS pairs as one memset of the summary block
+// and one launch; arena_cap = the usable entries of b.arena_h / b.arena_k, image = the batch's result image
+// (small_pass.h: small_image_capacity() bytes).  A finalised pass leaves every device array as launch_compare ..
+// launch_emit would; a declined one (image header) leaves them undefined and the ordinary pass runs again.
+hipError_t launch_small_pass(hipStream_t s, const DiffBuffers& b, uint64_t arena_cap, uint8_t* image);
 // profiling hook: the timeline build (gpudiff_k2_profile) of K2 writes 12 u64 per wave (start, first item end, items,
 // last item start, end, streaming ticks, join ticks, hw id, rows, pre, post, ticket ticks) into dev_buf
 // (cap_waves waves); nullptr disables

@@ -30,6 +30,9 @@ OPT_TIMING = 0x1
 OPT_DEVICE_ENCODE = 0x2000000
 OPT_PATH_STRINGS = 0x8000000  # device-encoded batches: K15/K16 render the changed paths as text (DiffResult.path_strings)
 OPT_ARENA_SHIFT = 21  # test hook: 4 bits, the K2 wave arenas shrunk 2^k-fold (forces the deferred K4 path)
+OPT_SMALL_PASS = 0x20000000  # a pass of 1..SMALL_PASS_MAX_PAIRS pairs runs as one kernel (K20) with one read-back
+SMALL_PASS_MAX_PAIRS = 4096  # GPUDIFF_SMALL_PASS_MAX_PAIRS
+SMALL_PASS_MAX_PATHS = 32768  # GPUDIFF_SMALL_PASS_MAX_PATHS: a small pass with more changed paths is redone
 DEVICE_CURRENT, DEVICE_NONE = -1, -2
 
 PATH_HASH_BITS = 32  # GPUDIFF_PATH_HASH_BITS: segment keys and reported path hashes
@@ -282,6 +285,16 @@ class PathStats(C.Structure):
                 ("kernel_ms", C.c_double), ("timed_batches", C.c_uint64)]
 
 
+class PassStats(C.Structure):
+    """gpudiff_pass_stats: the context's diff passes since open (OPT_SMALL_PASS)."""
+    _fields_ = [("passes", C.c_uint64), ("small_passes", C.c_uint64), ("small_redone", C.c_uint64),
+                ("redo_arena", C.c_uint64), ("redo_deep", C.c_uint64), ("redo_paths", C.c_uint64),
+                ("readback_rounds", C.c_uint64)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 class DeviceView(C.Structure):
     _fields_ = [("pair_flags", C.c_void_p), ("spec_dirty_ids", C.c_void_p), ("status_dirty_ids", C.c_void_p),
                 ("dirty_ids", C.c_void_p), ("counts", C.c_void_p)]
@@ -329,6 +342,7 @@ SIGNATURES = [
     ("gpudiff_result_path_strings", C.c_int, [_P, C.POINTER(Result), C.POINTER(PathStringsC)]),
     ("gpudiff_path_strings_stats_get", C.c_int, [_P, C.POINTER(PathStats)]),
     ("gpudiff_last_timings", C.c_int, [_P, C.POINTER(Timings)]),
+    ("gpudiff_pass_stats_get", C.c_int, [_P, C.POINTER(PassStats)]),
     ("gpudiff_sync", C.c_int, [_P]),
     ("gpudiff_timing_reset", C.c_int, [_P]),
     ("gpudiff_hbatch_create", C.c_int, [_P, C.c_uint64, C.c_size_t, C.c_uint64, C.POINTER(_P), C.POINTER(_P),
@@ -773,7 +787,7 @@ class Engine:
 
     def __init__(self, device: int = DEVICE_CURRENT, encode_threads: int = 0, stream: Optional[int] = None,
                  timing: bool = False, path_hash_bits: int = PATH_HASH_BITS, flags: int = 0,
-                 device_encode: bool = False):
+                 device_encode: bool = False, small_pass: bool = False):
         if stream is not None and not stream:
             # 0 is HIP's null stream, which the engine cannot share: gpudiff_open reads NULL as "create your
             # own (non-blocking) stream", and a non-blocking stream never orders against the null stream --
@@ -782,7 +796,8 @@ class Engine:
             raise ValueError("Engine(stream=0): the null stream cannot be shared; make a torch.cuda.Stream current "
                              "and pass its cuda_stream")
         o = Opts(device=device, encode_threads=encode_threads, stream=stream or None,
-                 flags=(OPT_TIMING if timing else 0) | (OPT_DEVICE_ENCODE if device_encode else 0) | flags,
+                 flags=(OPT_TIMING if timing else 0) | (OPT_DEVICE_ENCODE if device_encode else 0) |
+                 (OPT_SMALL_PASS if small_pass else 0) | flags,
                  path_hash_bits=path_hash_bits)
         h = C.c_void_p()
         _chk(_lib.gpudiff_open(C.byref(o), C.byref(h)), "gpudiff_open")
@@ -865,6 +880,12 @@ class Engine:
         """gpudiff_path_strings_stats_get: what OPT_PATH_STRINGS rendered so far (kernel_ms with timing)."""
         st = PathStats()
         _chk(_lib.gpudiff_path_strings_stats_get(self.ctx, C.byref(st)), "gpudiff_path_strings_stats_get")
+        return st
+
+    def pass_stats(self) -> PassStats:
+        """gpudiff_pass_stats_get: passes, fused small passes, the ones redone (by reason), read-back rounds."""
+        st = PassStats()
+        _chk(_lib.gpudiff_pass_stats_get(self.ctx, C.byref(st)), "gpudiff_pass_stats_get")
         return st
 
     def sync(self):
