@@ -114,9 +114,12 @@ enum {
                                                 (K20: decision, joins, compaction and path copy fused) and comes back
                                                 in one read-back; results are those of the ordinary pass, byte for
                                                 byte (gpudiff_pass_stats_get) */
+#define GPUDIFF_OPT_PATH_VALUES 0x80000000u   /* the scope of GPUDIFF_OPT_PATH_STRINGS, and independent of it: kernels
+                                                K21 / K22 render every changed leaf's old and new value as JSON text
+                                                inside gpudiff_wait (gpudiff_result_path_values) */
 #define GPUDIFF_OPT_KNOWN                                                                                         \
     (GPUDIFF_OPT_TIMING | (0xFu << GPUDIFF_OPT_ARENA_SHIFT) | GPUDIFF_OPT_DEVICE_ENCODE | GPUDIFF_OPT_PATH_STRINGS | \
-     GPUDIFF_OPT_SMALL_PASS)
+     GPUDIFF_OPT_SMALL_PASS | GPUDIFF_OPT_PATH_VALUES)
 
 /* GPUDIFF_OPT_SMALL_PASS: the largest pass the fused kernel takes (64 chunks of 64 pairs: its finishing block scans
  * the chunks with one lane each), and the most changed paths it finishes itself -- a pass with more is run again as
@@ -205,6 +208,42 @@ typedef struct gpudiff_path_stats {
     uint64_t timed_batches;
 } gpudiff_path_stats;
 int gpudiff_path_strings_stats_get(gpudiff_ctx* ctx, gpudiff_path_stats* out);
+
+/* ---- changed leaves' values as text (GPUDIFF_OPT_PATH_VALUES) ----
+ * For entry i of the batch's changed paths (path_hashes[i] / path_kinds[i]) two values, old (A's leaf) and new (B's
+ * leaf), rendered from the segments the blobs carry in HBM (gpudiff_format.h):
+ *
+ *   GPUDIFF_PATH_CHANGED         old = A's leaf   new = B's leaf
+ *   GPUDIFF_PATH_ADDED           old absent       new = B's leaf
+ *   GPUDIFF_PATH_REMOVED         old = A's leaf   new absent
+ *   GPUDIFF_PATH_STATUS_ABSENT   both absent
+ *
+ * A present value is a type tag (GPUDIFF_TAG_*, gpudiff_format.h) and a text, never empty: the bytes the write
+ * path's encoder (json.NewEncoder(w).Encode) puts on the wire for the leaf, rendered from the canonical value the
+ * blob stores -- null / false / true / {} / [], int64 digits, Go's shortest float64 form (a negative zero is stored
+ * as +0 and renders "0"), a string as '"' + HTML-safe escaping + '"'.  3 -> 3.0 is a CHANGED entry whose two texts
+ * are both "3" and whose tags differ (INT, FLOAT).  An absent value has tag GPUDIFF_VALUE_ABSENT and an empty text.
+ * Pairs the host resolved (K0's deferrals) get their values from the resolution batch's blobs, by the same kernels:
+ * n_host counts those entries.  n_unresolved counts values whose leaf was not found or whose segment did not check
+ * out (rendered ABSENT / empty): always 0 for blobs the engine wrote.
+ * The arrays belong to the result (valid until gpudiff_result_release).
+ * GPUDIFF_E_STATE: exactly the cases of gpudiff_result_path_strings. */
+#define GPUDIFF_VALUE_ABSENT 0xFFu
+typedef struct gpudiff_path_values {
+    size_t n_paths;            /* == result.n_paths */
+    const uint64_t* offsets;   /* 2 * n_paths + 1: text 2i = old of entry i, 2i + 1 = new */
+    const char* bytes;         /* packed, no terminators */
+    const uint8_t* tags;       /* 2 * n_paths: GPUDIFF_TAG_* or GPUDIFF_VALUE_ABSENT */
+    size_t n_host;             /* entries whose pair the host resolved */
+    size_t n_unresolved;       /* must be 0; such values are ABSENT / empty */
+} gpudiff_path_values;
+int gpudiff_result_path_values(gpudiff_ctx* ctx, const gpudiff_result* res, gpudiff_path_values* out);
+/* gpudiff_path_stats counted for the values: paths = entries, bytes = the texts' bytes, host_paths = n_host summed;
+ * kernel_ms (GPUDIFF_OPT_TIMING): HIP events around K21 + scan and around the offsets + K22 */
+int gpudiff_path_values_stats_get(gpudiff_ctx* ctx, gpudiff_path_stats* out);
+/* stream synchronisations the context's finishers spent on rendering text (strings and values together): with both
+ * options on, one batch's two sizing read-backs are one 16-byte copy and one synchronisation */
+int gpudiff_render_syncs_get(gpudiff_ctx* ctx, uint64_t* out);
 
 /* device-side view of a diffed batch (for RCCL gathers; pointers are HBM).  The pointers belong to the batch's
  * current result slot: after gpudiff_dbatch_result_slot switches slots, fetch the view again (counts included --
@@ -488,6 +527,13 @@ int gpudiff_encode_object_host(const uint8_t* doc, size_t len, uint32_t seed, ui
  * GPUDIFF_E_CAPACITY: the text is longer than cap, *out_len is still set. */
 int gpudiff_render_path_from_blob(const uint8_t* blob, const gpudiff_obj_info* info, uint32_t seed,
                                   uint64_t path_hash, char* buf, size_t cap, size_t* out_len);
+/* The value twin of gpudiff_render_path_from_blob: the leaf whose key is `path_hash` in the blob's spec
+ * (status_region == 0) or status segment, as *tag and the text gpudiff_result_path_values gives, *out_len bytes into
+ * buf, no terminator.  No GPU needed: the routine kernels K21 / K22 run, on the host.
+ * GPUDIFF_E_NOTFOUND: the hash is not in that region's keys, or the leaf's record does not check out;
+ * GPUDIFF_E_CAPACITY: the text is longer than cap, *out_len is still set; GPUDIFF_E_STATE: the object was not encoded. */
+int gpudiff_render_value_from_blob(const uint8_t* blob, const gpudiff_obj_info* info, uint32_t status_region,
+                                   uint64_t path_hash, uint8_t* tag, char* buf, size_t cap, size_t* out_len);
 /* profiling hook: K0 per-phase wall-clock ticks (100 MHz, summed over waves) since the
  * previous call (scan, tree, values, hashes, sort, blob, -, -); enable != 0
  * keeps recording */

@@ -301,6 +301,8 @@ type Batcher struct {
 	// onPaths (WithPaths): called for every dirty event, before its enqueue, with the event's changed field
 	// paths as the engine rendered them (OptPathStrings on a device-encode engine / store)
 	onPaths func(obj interface{}, paths []ChangedPath)
+	// onValues (WithValues): the same for the changed leaves' old and new values (OptPathValues)
+	onValues func(obj interface{}, values []ChangedValue)
 }
 
 // ChangedPath is one entry of a dirty pair's changed-path list with its text ("spec.replicas", raw key bytes).
@@ -342,6 +344,62 @@ func (e *Engine) PathStrings(res *C.gpudiff_result) [][]ChangedPath {
 			txt := C.GoStringN((*C.char)(unsafe.Pointer(uintptr(unsafe.Pointer(ps.bytes))+uintptr(offs[q]))),
 				C.int(offs[q+1]-offs[q]))
 			out[k] = append(out[k], ChangedPath{Hash: uint64(hs[q]), Kind: uint8(ks[q]), Path: txt})
+		}
+	}
+	return out
+}
+
+// ChangedValue is one entry of a dirty pair's changed-path list with the JSON text of the old (A's) and the new
+// (B's) leaf, as the write path's encoder would put them on the wire.  A side that has no such leaf (ADDED: old,
+// REMOVED: new, the status sentinel: both) has tag ValueAbsent and an empty text.
+type ChangedValue struct {
+	Hash   uint64
+	Kind   uint8 // GPUDIFF_PATH_* | GPUDIFF_PATH_REGION_STATUS
+	OldTag uint8 // GPUDIFF_TAG_* or ValueAbsent
+	Old    string
+	NewTag uint8
+	New    string
+}
+
+// ValueAbsent is the tag of a value that is not there (GPUDIFF_VALUE_ABSENT).
+const ValueAbsent = uint8(C.GPUDIFF_VALUE_ABSENT)
+
+// OptPathValues (the scope of OptPathStrings, and independent of it): kernels K21 / K22 render every changed leaf's
+// old and new value as JSON text inside gpudiff_wait; the batcher hands them to WithValues' callback.
+const OptPathValues = uint32(C.GPUDIFF_OPT_PATH_VALUES)
+
+// WithValues sets the callback that receives each dirty event's changed values (PathValues below); without
+// OptPathValues, or for a batch the engine encoded on the host, it is never called.
+func (b *Batcher) WithValues(fn func(obj interface{}, values []ChangedValue)) *Batcher {
+	b.onValues = fn
+	return b
+}
+
+// PathValues copies a waited result's changed values out, per dirty pair in result order (nil when the engine
+// rendered none: gpudiff_result_path_values returns GPUDIFF_E_STATE).  Call before gpudiff_result_release.
+func (e *Engine) PathValues(res *C.gpudiff_result) [][]ChangedValue {
+	var pv C.gpudiff_path_values
+	if C.gpudiff_result_path_values(e.ctx, res, &pv) != C.GPUDIFF_OK {
+		return nil
+	}
+	nd, np := int(res.n_dirty), int(pv.n_paths)
+	out := make([][]ChangedValue, nd)
+	if np == 0 {
+		return out
+	}
+	poff := (*[1 << 28]C.uint32_t)(unsafe.Pointer(res.path_offsets))[: nd+1 : nd+1]
+	hs := (*[1 << 28]C.uint64_t)(unsafe.Pointer(res.path_hashes))[:np:np]
+	ks := (*[1 << 30]C.uint8_t)(unsafe.Pointer(res.path_kinds))[:np:np]
+	offs := (*[1 << 28]C.uint64_t)(unsafe.Pointer(pv.offsets))[: 2*np+1 : 2*np+1]
+	tags := (*[1 << 30]C.uint8_t)(unsafe.Pointer(pv.tags))[: 2*np : 2*np]
+	text := func(t int) string {
+		return C.GoStringN((*C.char)(unsafe.Pointer(uintptr(unsafe.Pointer(pv.bytes))+uintptr(offs[t]))),
+			C.int(offs[t+1]-offs[t]))
+	}
+	for k := 0; k < nd; k++ {
+		for q := int(poff[k]); q < int(poff[k+1]); q++ {
+			out[k] = append(out[k], ChangedValue{Hash: uint64(hs[q]), Kind: uint8(ks[q]), OldTag: uint8(tags[2*q]),
+				Old: text(2 * q), NewTag: uint8(tags[2*q+1]), New: text(2*q + 1)})
 		}
 	}
 	return out
@@ -658,6 +716,7 @@ func (b *Batcher) submitFlight(evs []event) *flight {
 func (b *Batcher) finishFlight(f *flight) {
 	flags := make([]uint8, f.n)
 	var paths map[int][]ChangedPath // OptPathStrings + WithPaths: pair index -> its changed paths
+	var values map[int][]ChangedValue // OptPathValues + WithValues: pair index -> its changed values
 	rc := f.rc
 	if f.n > 0 {
 		b.e.mu.Lock()
@@ -676,6 +735,15 @@ func (b *Batcher) finishFlight(f *flight) {
 					}
 				}
 			}
+			if b.onValues != nil {
+				if pv := b.e.PathValues(&res); pv != nil {
+					ids := (*[1 << 28]C.uint32_t)(unsafe.Pointer(res.dirty_ids))[:len(pv):len(pv)]
+					values = make(map[int][]ChangedValue, len(pv))
+					for k := range pv {
+						values[int(ids[k])] = pv[k]
+					}
+				}
+			}
 			C.gpudiff_result_release(b.e.ctx, &res)
 		}
 		b.e.mu.Unlock()
@@ -685,6 +753,9 @@ func (b *Batcher) finishFlight(f *flight) {
 		if k < 0 || rc != C.GPUDIFF_OK || !f.ok[k] || flags[k]&uint8(ev.which) != 0 {
 			if p, have := paths[k]; have && f.ok[k] {
 				b.onPaths(ev.new, p)
+			}
+			if v, have := values[k]; have && f.ok[k] {
+				b.onValues(ev.new, v)
 			}
 			ev.enqueue(ev.new)
 		}

@@ -1013,6 +1013,34 @@ int gpudiff_path_strings_stats_get(gpudiff_ctx* c, gpudiff_path_stats* out) {
     return GPUDIFF_OK;
 }
 
+int gpudiff_result_path_values(gpudiff_ctx* c, const gpudiff_result* res, gpudiff_path_values* out) {
+    (void)c;
+    if (!res || !out) return GPUDIFF_E_INVAL;
+    memset(out, 0, sizeof(*out));
+    const ResultStore* rs = (const ResultStore*)res->internal_;
+    // rendered by the device-encode finisher only (dstore.cpp), as the strings are
+    if (!rs || !rs->pv.on) return GPUDIFF_E_STATE;
+    out->n_paths = rs->pv.n;
+    out->offsets = rs->pv.offsets();
+    out->bytes = rs->pv.bytes();
+    out->tags = rs->pv.tags();
+    out->n_host = rs->pv.n_host;
+    out->n_unresolved = rs->pv.n_unresolved;
+    return GPUDIFF_OK;
+}
+
+int gpudiff_path_values_stats_get(gpudiff_ctx* c, gpudiff_path_stats* out) {
+    if (!c || !out) return GPUDIFF_E_INVAL;
+    *out = c->value_stats;  // all zero while the option is off
+    return GPUDIFF_OK;
+}
+
+int gpudiff_render_syncs_get(gpudiff_ctx* c, uint64_t* out) {
+    if (!c || !out) return GPUDIFF_E_INVAL;
+    *out = c->render_syncs;
+    return GPUDIFF_OK;
+}
+
 void gpudiff_result_release(gpudiff_ctx* c, gpudiff_result* res) {
     (void)c;
     if (!res) return;

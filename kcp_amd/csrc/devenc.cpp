@@ -8,8 +8,13 @@
 #include "engine.h"
 #include "pathstr.h"
 #include "tokenize.h"
+#include "valstr.h"
 
 using namespace gd;
+
+namespace gd {
+uint32_t go_float_text(double f, char* out);  // upsert.cpp: the write path's Go-exact float formatter
+}
 
 namespace {
 
@@ -17,6 +22,18 @@ struct DevBuf {
     void* p = nullptr;
     ~DevBuf() {
         if (p) (void)hipFree(p);
+    }
+};
+
+// valstr.h's float formatter on the host
+struct HostFloat {
+    uint64_t operator()(uint64_t bits, uint8_t* o) const {
+        double f;
+        memcpy(&f, &bits, 8);
+        char b[32];
+        const uint32_t n = go_float_text(f, b);
+        if (o && n <= sizeof(b)) memcpy(o, b, n);
+        return n <= sizeof(b) ? n : kValUnresolved;
     }
 };
 
@@ -70,6 +87,26 @@ int gpudiff_render_path_from_blob(const uint8_t* blob, const gpudiff_obj_info* i
     if (out_len) *out_len = (size_t)len;
     if (len > cap) return GPUDIFF_E_CAPACITY;
     return path_text_write(t, seed, path_hash, (uint8_t*)buf, len) ? GPUDIFF_OK : GPUDIFF_E_NOTFOUND;
+}
+
+int gpudiff_render_value_from_blob(const uint8_t* blob, const gpudiff_obj_info* info, uint32_t status_region,
+                                   uint64_t path_hash, uint8_t* tag, char* buf, size_t cap, size_t* out_len) {
+    if (!blob || !info || (cap && !buf)) return GPUDIFF_E_INVAL;
+    if (out_len) *out_len = 0;
+    if (tag) *tag = GPUDIFF_VALUE_ABSENT;
+    if (info->status != GPUDIFF_TOK_OK) return GPUDIFF_E_STATE;
+    const ValSeg sg = val_seg(blob, info->bytes, info->spec_l, info->spec_ar, info->stat_l, info->stat_ar,
+                              status_region != 0);
+    if (!sg.ok) return GPUDIFF_E_NOTFOUND;
+    const uint32_t idx = val_find(sg, path_hash);
+    if (idx == kValNoLeaf) return GPUDIFF_E_NOTFOUND;
+    const ValLeaf v = val_leaf(sg, idx, val_arena_prefix(sg, idx));
+    const uint64_t len = val_text_len(v, HostFloat());
+    if (len == kValUnresolved) return GPUDIFF_E_NOTFOUND;
+    if (tag) *tag = (uint8_t)v.tag;
+    if (out_len) *out_len = (size_t)len;
+    if (len > cap) return GPUDIFF_E_CAPACITY;
+    return val_text_write(v, (uint8_t*)buf, len, HostFloat()) ? GPUDIFF_OK : GPUDIFF_E_NOTFOUND;
 }
 
 int gpudiff_encode_objects(gpudiff_ctx* c, const uint8_t* const* docs, const size_t* lens, const uint32_t* seeds,

@@ -23,7 +23,8 @@
 //
 // dstore_submit drives these phases, in order: refuse_if_strings_need_compaction, claim_ring_slot,
 // build_tables_pairs | build_tables_store, plan_upload (dstore_plan.h), grow_batch_buffers, stage_and_encode,
-// link_and_diff; the ticket's finisher is finish_batch.  resolve (from finish_batch, when K0 deferred events):
+// link_and_diff; the ticket's finisher is finish_batch (render_text: the changed paths and values as text).  resolve
+// (from finish_batch, when K0 deferred events):
 // encode_deferred_pair | encode_deferred_store per event, slot_updates, place_conservative | place_and_diff,
 // merge_results.
 //
@@ -35,6 +36,7 @@
 #include "pathstr.h"
 #include "plan.h"
 #include "scan64.h"
+#include "values.h"
 
 #include <emmintrin.h>
 #include <string.h>
@@ -52,6 +54,25 @@
 using namespace gd;
 
 namespace {
+
+// GPUDIFF_OPT_PATH_VALUES: K21 / K22's device buffers for one batch (a ring slot's, or the resolution batch's),
+// cached and grown on demand, never allocated per batch
+struct ValBufs {
+    uint64_t* len = nullptr;     // K21: the texts' lengths [2n]
+    uint64_t* tiles = nullptr;   // the scan's tile sums
+    ValueSlot* slots = nullptr;  // K21's (leaf index, arena offset) per entry and side
+    uint8_t* tags = nullptr;     // K21's tags [2n] (copied into out once it is sized)
+    uint8_t* out = nullptr;      // offsets[2n + 1] | tags[2n], padded to 8 | bytes: one D2H
+    uint64_t len_cap = 0, tiles_cap = 0, slots_cap = 0, tags_cap = 0, out_cap = 0;
+    unsigned long long* ctr = nullptr;  // the resolution batch's own: total bytes, unresolved values
+    hipEvent_t ev[4] = {};       // GPUDIFF_OPT_TIMING: K21 + scan begin/end, offsets + K22 begin/end
+    void free_all() {
+        for (void* p : {(void*)len, (void*)tiles, (void*)slots, (void*)tags, (void*)out, (void*)ctr})
+            if (p) (void)hipFree(p);
+        for (auto& e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
 
 struct Ring {
     gpudiff_dbatch* d = nullptr;  // rows, pair_ids, results; pool = the store's current space
@@ -82,17 +103,21 @@ struct Ring {
     uint64_t bound = 0;
     gpudiff_ticket ticket = 0;
     bool outstanding = false;
-    // GPUDIFF_OPT_PATH_STRINGS (render_paths): cached here and grown on demand, never allocated per batch
+    // GPUDIFF_OPT_PATH_STRINGS (render_text): cached here and grown on demand, never allocated per batch
     bool strs = false;            // this batch was submitted with the option on
     uint32_t space_idx = 0;       // the space its blobs were written to
     uint32_t* dntab = nullptr;    // K0x: per row, the path-table entry counts of its old and new blob
     uint64_t ntab_cap = 0;
     uint64_t* ps_len = nullptr;   // K15: the strings' lengths
     uint64_t* ps_tiles = nullptr;  // the scan's tile sums
-    unsigned long long* ps_ctr = nullptr;  // total bytes, unresolved entries
+    // the renderers' counters, one block so both totals come back in one 16-byte copy: the values' bytes, the
+    // strings' bytes, the strings' unresolved entries (K15 / K16 own [1..2]), the values' unresolved
+    unsigned long long* tx_ctr = nullptr;
     uint8_t* ps_out = nullptr;    // offsets[n + 1] | bytes: one D2H
     uint64_t ps_len_cap = 0, ps_tiles_cap = 0, ps_out_cap = 0;
     hipEvent_t ps_ev[4] = {};     // GPUDIFF_OPT_TIMING: K15 + scan begin/end, offsets + K16 begin/end
+    bool vals = false;            // GPUDIFF_OPT_PATH_VALUES: this batch was submitted with the option on
+    ValBufs vb;
     // gpudiff_store_write_plan_get (dstore_write_plan): what submit and wait keep for it -- the tables' extent and
     // the host-resolved rows' final flags, nothing per event -- and its device buffers, cached and grown on demand
     uint32_t nd = 0;              // staged documents of the batch (TokDoc[nd] at dmeta, DocLink[nd] at links_off)
@@ -188,6 +213,7 @@ struct DStore {
     gpudiff_dbatch* res_d = nullptr;
     uint8_t* res_stage = nullptr;
     uint64_t res_stage_cap = 0;
+    ValBufs res_vb;  // GPUDIFF_OPT_PATH_VALUES: the resolution batch's values
     SlotUpdate* res_ups = nullptr;
     uint64_t res_ups_cap = 0;
     uint32_t* res_err = nullptr;
@@ -249,10 +275,11 @@ int grow_dev(T** p, uint64_t* cap, uint64_t need) {
 // exact append point back
 int compact(DStore* s) {
     gpudiff_ctx* c = s->c;
-    // GPUDIFF_OPT_PATH_STRINGS: a batch in flight renders its paths from the space it was written to; packing into
-    // that space would overwrite its superseded blobs first (dstore_submit refuses such a submit before it gets here)
+    // GPUDIFF_OPT_PATH_STRINGS / _VALUES: a batch in flight renders its text from the space it was written to; packing
+    // into that space would overwrite its superseded blobs first (dstore_submit refuses such a submit before it gets
+    // here)
     for (const Ring& R : s->ring)
-        if (R.outstanding && R.strs && R.space_idx == 1 - s->cur) return GPUDIFF_E_STATE;
+        if (R.outstanding && (R.strs || R.vals) && R.space_idx == 1 - s->cur) return GPUDIFF_E_STATE;
     HIPCHK(launch_compact_store(c->stream, s->slots, s->max_slots, s->space[s->cur], s->space[1 - s->cur], s->sizes,
                                 s->tile_sums, s->used_dev));
     s->cur = 1 - s->cur;
@@ -274,60 +301,191 @@ int ensure_space(DStore* s, uint64_t want, uint64_t need) {
     return s->used_ub + need <= s->space_bytes ? GPUDIFF_OK : GPUDIFF_E_CAPACITY;
 }
 
-// ------------------------------------------------------------------ changed paths as text
-// GPUDIFF_OPT_PATH_STRINGS: K15 + scan + K16 (paths.hip) over a waited batch's changed-path lists, on the readback
-// stream (never behind the next batch's work).  Runs in the finisher between collect_results (the counts; the diff
-// pass is done) and resolve(): until then the batch's rows, its changed-path lists and both sides' blobs are as the
-// diff pass read them, in the space the batch was written to (R.d->pool) -- DESIGN.md "Changed paths as text".
-int render_paths(DStore* s, Ring& R, ResultStore& rs) {
-    gpudiff_ctx* c = s->c;
-    gpudiff_dbatch* d = R.d;
-    PathStrs& ps = rs.ps;
-    ps.on = true;
-    ps.n = rs.hashes.size();
-    ps.words.assign(1, 0);
-    c->path_stats.batches++;
-    if (!ps.n) return GPUDIFF_OK;
-    if (ps.n > 0xFFFFFFFFull) return GPUDIFF_E_CAPACITY;
+// ------------------------------------------------------------------ changed paths and values as text
+// GPUDIFF_OPT_PATH_STRINGS: K15 + scan + K16 (paths.hip), GPUDIFF_OPT_PATH_VALUES: K21 + scan + K22 (values.hip), over
+// a waited batch's changed-path lists, on the readback stream (never behind the next batch's work).  Runs in the
+// finisher between collect_results (the counts; the diff pass is done) and resolve(): until then the batch's rows, its
+// changed-path lists and both sides' blobs are as the diff pass read them, in the space the batch was written to
+// (R.d->pool) -- DESIGN.md "Changed paths as text", "Changed values as text".
+//
+// Each renderer is two enqueues around one sizing read-back: lengths + the scan's sums, then (the total known, the
+// output grown) the offsets + the write and the copy home.  With both options on the two length passes run first and
+// both totals come back in one 16-byte copy and one synchronisation.
+int paths_len(gpudiff_ctx* c, Ring& R, const PathJob& j, hipStream_t st, bool timing) {
     int rc;
-    const uint32_t n = (uint32_t)ps.n;
-    if ((rc = grow_dev(&R.ps_len, &R.ps_len_cap, n)) || (rc = grow_dev(&R.ps_tiles, &R.ps_tiles_cap, scan64_tiles(n) + 1)))
+    if ((rc = grow_dev(&R.ps_len, &R.ps_len_cap, j.n_paths)) ||
+        (rc = grow_dev(&R.ps_tiles, &R.ps_tiles_cap, scan64_tiles(j.n_paths) + 1)))
         return rc;
-    if (!R.ps_ctr && (rc = dalloc(&R.ps_ctr, 2))) return rc;
-    const bool timing = (c->flags & GPUDIFF_OPT_TIMING) != 0;
     if (timing && !R.ps_ev[0])
         for (auto& e : R.ps_ev) HIPCHK(hipEventCreate(&e));
-    PathJob j{d->rows,     R.dntab,      d->dirty_idx,  d->path_off,           d->out_h, d->out_k,
-              d->pool,     d->pool_cap,  c->hash_mask,  (uint32_t)rs.dirty.size(), n};
-    hipStream_t st = c->rb;
-    unsigned long long ctr[2] = {0, 0};
     if (timing) HIPCHK(hipEventRecord(R.ps_ev[0], st));
-    HIPCHK(launch_path_len(st, j, R.ps_len, R.ps_tiles, R.ps_ctr));
+    HIPCHK(launch_path_len(st, j, R.ps_len, R.ps_tiles, R.tx_ctr + 1));
     if (timing) HIPCHK(hipEventRecord(R.ps_ev[1], st));
-    HIPCHK(hipMemcpyAsync(ctr, R.ps_ctr, 8, hipMemcpyDeviceToHost, st));  // the bytes to make room for
-    HIPCHK(hipStreamSynchronize(st));
-    const uint64_t head = 8ull * ((uint64_t)n + 1), total = ctr[0];
+    return GPUDIFF_OK;
+}
+
+int paths_write(Ring& R, const PathJob& j, uint64_t total, hipStream_t st, bool timing, PathStrs& ps) {
+    int rc;
+    const uint64_t head = 8ull * ((uint64_t)j.n_paths + 1);
     if ((rc = grow_dev(&R.ps_out, &R.ps_out_cap, head + total + 8))) return rc;
     if (timing) HIPCHK(hipEventRecord(R.ps_ev[2], st));
-    HIPCHK(launch_path_write(st, j, R.ps_len, R.ps_tiles, (uint64_t*)R.ps_out, R.ps_out + head, total, R.ps_ctr));
+    HIPCHK(launch_path_write(st, j, R.ps_len, R.ps_tiles, (uint64_t*)R.ps_out, R.ps_out + head, total, R.tx_ctr + 1));
     if (timing) HIPCHK(hipEventRecord(R.ps_ev[3], st));
     try {
-        ps.words.assign((size_t)n + 1 + (size_t)((total + 7) / 8), 0);
+        ps.words.assign((size_t)j.n_paths + 1 + (size_t)((total + 7) / 8), 0);
     } catch (const std::bad_alloc&) {
         return GPUDIFF_E_NOMEM;
     }
     HIPCHK(hipMemcpyAsync(ps.words.data(), R.ps_out, head + total, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(ctr, R.ps_ctr, 16, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    ps.n_unresolved = (size_t)ctr[1];
-    if (ps.words[n] != total) return GPUDIFF_E_DEVICE;  // the offsets the strings were written by
-    if (timing) {
-        float a = 0, b = 0;
-        HIPCHK(hipEventElapsedTime(&a, R.ps_ev[0], R.ps_ev[1]));
-        HIPCHK(hipEventElapsedTime(&b, R.ps_ev[2], R.ps_ev[3]));
-        c->path_stats.kernel_ms += (double)a + b;
-        c->path_stats.timed_batches++;
+    return GPUDIFF_OK;
+}
+
+// kernel time of one renderer's two event pairs into its stats
+int add_kernel_ms(const hipEvent_t* ev, gpudiff_path_stats& st) {
+    float a = 0, b = 0;
+    HIPCHK(hipEventElapsedTime(&a, ev[0], ev[1]));
+    HIPCHK(hipEventElapsedTime(&b, ev[2], ev[3]));
+    st.kernel_ms += (double)a + b;
+    return GPUDIFF_OK;
+}
+
+// the values' buffers: out of device memory is GPUDIFF_E_CAPACITY
+template <class T>
+int grow_val(T** p, uint64_t* cap, uint64_t need) {
+    if (grow_dev(p, cap, need) == GPUDIFF_OK) return GPUDIFF_OK;
+    (void)hipGetLastError();
+    return GPUDIFF_E_CAPACITY;
+}
+
+int values_len(ValBufs& B, const ValueJob& j, hipStream_t st, bool timing, unsigned long long* total,
+               unsigned long long* unresolved) {
+    int rc;
+    const uint64_t n2 = 2ull * j.n_paths;
+    if ((rc = grow_val(&B.len, &B.len_cap, n2)) ||
+        (rc = grow_val(&B.tiles, &B.tiles_cap, scan64_tiles((uint32_t)n2) + 1)) ||
+        (rc = grow_val(&B.slots, &B.slots_cap, n2)) || (rc = grow_val(&B.tags, &B.tags_cap, n2)))
+        return rc;
+    if (timing && !B.ev[0])
+        for (auto& e : B.ev) HIPCHK(hipEventCreate(&e));
+    if (timing) HIPCHK(hipEventRecord(B.ev[0], st));
+    HIPCHK(launch_value_len(st, j, B.tags, B.len, B.slots, B.tiles, total, unresolved));
+    if (timing) HIPCHK(hipEventRecord(B.ev[1], st));
+    return GPUDIFF_OK;
+}
+
+int values_write(ValBufs& B, const ValueJob& j, uint64_t total, hipStream_t st, bool timing,
+                 unsigned long long* unresolved, PathVals& pv) {
+    int rc;
+    const uint64_t n2 = 2ull * j.n_paths, head = 8ull * (n2 + 1 + PathVals::tag_words(j.n_paths));
+    if ((rc = grow_val(&B.out, &B.out_cap, head + total + 8))) return rc;
+    if (timing) HIPCHK(hipEventRecord(B.ev[2], st));
+    HIPCHK(hipMemsetAsync(B.out + 8ull * (n2 + 1), 0, 8ull * PathVals::tag_words(j.n_paths), st));
+    HIPCHK(hipMemcpyAsync(B.out + 8ull * (n2 + 1), B.tags, n2, hipMemcpyDeviceToDevice, st));
+    HIPCHK(launch_value_write(st, j, B.tags, B.len, B.slots, B.tiles, (uint64_t*)B.out, B.out + head, total,
+                              unresolved));
+    if (timing) HIPCHK(hipEventRecord(B.ev[3], st));
+    try {
+        pv.words.assign((size_t)(head / 8) + (size_t)((total + 7) / 8), 0);
+    } catch (const std::bad_alloc&) {
+        return GPUDIFF_E_NOMEM;
     }
+    HIPCHK(hipMemcpyAsync(pv.words.data(), B.out, head + total, hipMemcpyDeviceToHost, st));
+    return GPUDIFF_OK;
+}
+
+ValueJob value_job(const gpudiff_ctx* c, const gpudiff_dbatch* d, size_t n_dirty, uint32_t n) {
+    return ValueJob{d->rows, d->dirty_idx, d->path_off, d->out_h, d->out_k, d->pool, d->pool_cap, c->hash_mask,
+                    (uint32_t)n_dirty, n};
+}
+
+int render_text(DStore* s, Ring& R, ResultStore& rs) {
+    gpudiff_ctx* c = s->c;
+    gpudiff_dbatch* d = R.d;
+    PathStrs& ps = rs.ps;
+    PathVals& pv = rs.pv;
+    const size_t np = rs.hashes.size();
+    if (R.strs) {
+        ps.on = true;
+        ps.n = np;
+        ps.words.assign(1, 0);
+        c->path_stats.batches++;
+    }
+    if (R.vals) {
+        pv.on = true;
+        pv.n = np;
+        pv.words.assign(1, 0);
+        c->value_stats.batches++;
+    }
+    if (!np) return GPUDIFF_OK;
+    if (np > 0x7FFFFFFFull) return GPUDIFF_E_CAPACITY;
+    int rc;
+    const uint32_t n = (uint32_t)np;
+    if (!R.tx_ctr && (rc = dalloc(&R.tx_ctr, 4))) return rc;
+    const bool timing = (c->flags & GPUDIFF_OPT_TIMING) != 0;
+    const PathJob j{d->rows,     R.dntab,      d->dirty_idx,  d->path_off,           d->out_h, d->out_k,
+                    d->pool,     d->pool_cap,  c->hash_mask,  (uint32_t)rs.dirty.size(), n};
+    const ValueJob vj = value_job(c, d, rs.dirty.size(), n);
+    hipStream_t st = c->rb;
+    unsigned long long ctr[4] = {0, 0, 0, 0};
+    if (R.strs && (rc = paths_len(c, R, j, st, timing))) return rc;
+    if (R.vals && (rc = values_len(R.vb, vj, st, timing, R.tx_ctr, R.tx_ctr + 3))) return rc;
+    HIPCHK(hipMemcpyAsync(ctr, R.tx_ctr, 16, hipMemcpyDeviceToHost, st));  // the bytes to make room for, both kinds
+    HIPCHK(hipStreamSynchronize(st));
+    c->render_syncs++;
+    const uint64_t vtotal = R.vals ? ctr[0] : 0, ptotal = R.strs ? ctr[1] : 0;
+    if (R.strs && (rc = paths_write(R, j, ptotal, st, timing, ps))) return rc;
+    if (R.vals && (rc = values_write(R.vb, vj, vtotal, st, timing, R.tx_ctr + 3, pv))) return rc;
+    HIPCHK(hipMemcpyAsync(ctr, R.tx_ctr, 32, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    c->render_syncs++;
+    if (R.strs) {
+        ps.n_unresolved = (size_t)ctr[2];
+        if (ps.words[n] != ptotal) return GPUDIFF_E_DEVICE;  // the offsets the strings were written by
+        if (timing) {
+            if ((rc = add_kernel_ms(R.ps_ev, c->path_stats))) return rc;
+            c->path_stats.timed_batches++;
+        }
+    }
+    if (R.vals) {
+        pv.n_unresolved = (size_t)ctr[3];
+        if (pv.words[2 * (size_t)n] != vtotal) return GPUDIFF_E_DEVICE;
+        if (timing) {
+            if ((rc = add_kernel_ms(R.vb.ev, c->value_stats))) return rc;
+            c->value_stats.timed_batches++;
+        }
+    }
+    return GPUDIFF_OK;
+}
+
+// The resolution batch's values (place_and_diff): the same two kernels over s->res_d, whose blobs -- host-written,
+// or a slot's resident one -- are all in HBM.
+int render_values_resolved(DStore* s, const ResultStore& r2, PathVals& pv) {
+    gpudiff_ctx* c = s->c;
+    ValBufs& B = s->res_vb;
+    const size_t np = r2.hashes.size();
+    pv.on = true;
+    pv.n = np;
+    pv.words.assign(1, 0);
+    if (!np) return GPUDIFF_OK;
+    if (np > 0x7FFFFFFFull) return GPUDIFF_E_CAPACITY;
+    int rc;
+    if (!B.ctr && (rc = dalloc(&B.ctr, 2))) return rc;
+    const bool timing = (c->flags & GPUDIFF_OPT_TIMING) != 0;
+    const ValueJob vj = value_job(c, s->res_d, r2.dirty.size(), (uint32_t)np);
+    hipStream_t st = c->rb;
+    unsigned long long ctr[2] = {0, 0};
+    if ((rc = values_len(B, vj, st, timing, B.ctr, B.ctr + 1))) return rc;
+    HIPCHK(hipMemcpyAsync(ctr, B.ctr, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    c->render_syncs++;
+    const uint64_t total = ctr[0];
+    if ((rc = values_write(B, vj, total, st, timing, B.ctr + 1, pv))) return rc;
+    HIPCHK(hipMemcpyAsync(ctr, B.ctr, 16, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    c->render_syncs++;
+    pv.n_unresolved = (size_t)ctr[1];
+    if (pv.words[2 * np] != total) return GPUDIFF_E_DEVICE;
+    if (timing && (rc = add_kernel_ms(B.ev, c->value_stats))) return rc;
     return GPUDIFF_OK;
 }
 
@@ -444,6 +602,7 @@ struct Deferred {
     // GPUDIFF_OPT_PATH_STRINGS: these events' strings come from the objects flattened here (their blobs carry no
     // table in pair mode, the re-encoded old side none in store mode)
     bool strs = false;
+    bool vals = false;  // GPUDIFF_OPT_PATH_VALUES: place_and_diff renders the resolution batch's values
     std::vector<HostPaths> hp;  // [drows.size()], or empty
     std::unordered_map<uint32_t, HostSlot> hs;
     std::vector<uint32_t> touched;  // hs's slots in first-touch order
@@ -614,6 +773,8 @@ int place_and_diff(DStore* s, const Deferred& W, const std::vector<SlotUpdate>& 
     if ((rc = collect_results(c, d, r2))) return rc;
     c->tickets.erase(t2);
     d->ticket = 0;
+    // the values of these events' changed leaves: the rows k_place wrote name blobs that are all in HBM
+    if (W.vals && (rc = render_values_resolved(s, r2, r2.pv))) return rc;
     uint32_t err = 0;
     HIPCHK(hipMemcpy(&err, s->res_err, 4, hipMemcpyDeviceToHost));
     return err ? GPUDIFF_E_CAPACITY : GPUDIFF_OK;
@@ -630,6 +791,11 @@ void merge_results(const Ring& R, const Deferred& W, ResultStore& rs, const Resu
         out.ps.on = true;
         out.ps.n_unresolved = rs.ps.n_unresolved;
         out.ps.begin();
+    }
+    if (W.vals) {
+        out.pv.on = true;
+        out.pv.n_unresolved = rs.pv.n_unresolved + (r2 ? r2->pv.n_unresolved : 0);
+        out.pv.begin();
     }
     size_t jr = 0, j2 = 0, k = 0;
     for (uint32_t i = 0; i < R.nev; i++) {
@@ -662,6 +828,12 @@ void merge_results(const Ring& R, const Deferred& W, ResultStore& rs, const Resu
         for (uint32_t q = lo; q < hi; q++) {
             out.hashes.push_back(src->hashes[q]);
             out.kinds.push_back(src->kinds[q]);
+            if (W.vals) {  // both branches carry what the device rendered: the batch's pass, or the resolution's
+                const PathVals& v = src->pv;
+                for (size_t t = 2 * (size_t)q; t < 2 * (size_t)q + 2; t++)
+                    out.pv.push(v.tags()[t], v.bytes() + v.offsets()[t], v.offsets()[t + 1] - v.offsets()[t]);
+                if (src == r2) out.pv.n_host++;
+            }
             if (!W.strs) continue;
             if (src == r2) host_path(W.hp[kd], *r2, q, mask, out.ps);
             else out.ps.push(rs.ps.bytes() + rs.ps.offsets()[q], rs.ps.offsets()[q + 1] - rs.ps.offsets()[q]);
@@ -669,6 +841,7 @@ void merge_results(const Ring& R, const Deferred& W, ResultStore& rs, const Resu
         out.off.push_back((uint32_t)out.hashes.size());
     }
     if (W.strs) out.ps.finish();
+    if (W.vals) out.pv.finish();
     rs = std::move(out);
 }
 
@@ -685,6 +858,7 @@ int resolve(DStore* s, Ring& R, ResultStore& rs) {
     s->deferred_total += W.drows.size();
     W.rows.resize(W.drows.size());
     W.strs = rs.ps.on;
+    W.vals = rs.pv.on;
     W.hp.resize(W.strs ? W.drows.size() : 0);
     int rc;
     for (size_t k = 0; k < W.drows.size(); k++) {
@@ -810,9 +984,9 @@ struct BatchTables {
 // into that space: a submit that may need one is refused before it changes anything (wait on the outstanding
 // ticket first).
 bool refuse_if_strings_need_compaction(const DStore* s, const gpudiff_event* ev, size_t n) {
-    if (s->pair_mode || !(s->c->flags & GPUDIFF_OPT_PATH_STRINGS)) return false;
+    if (s->pair_mode || !(s->c->flags & (GPUDIFF_OPT_PATH_STRINGS | GPUDIFF_OPT_PATH_VALUES))) return false;
     const Ring& O = s->ring[s->ring_next ^ 1u];
-    if (!(O.outstanding && O.strs && O.space_idx != s->cur)) return false;
+    if (!(O.outstanding && (O.strs || O.vals) && O.space_idx != s->cur)) return false;
     uint64_t pre = 0;  // >= the bound ensure_space is asked for
     for (size_t i = 0; i < n; i++)
         pre += (5 * ((uint64_t)ev[i].new_len + (ev[i].old_json ? ev[i].old_len : 0))) / 2 + 768;
@@ -1230,13 +1404,18 @@ int finish_batch(DStore* s, Ring& R, ResultStore& rs) {
         s->t_n++;
     }
     // the strings before resolve(): its compaction may pack into the space this batch's superseded blobs are in
-    int rc = R.strs ? render_paths(s, R, rs) : GPUDIFF_OK;
+    int rc = (R.strs || R.vals) ? render_text(s, R, rs) : GPUDIFF_OK;
     R.plan_patch.clear();
     if (!rc && ndef) rc = resolve(s, R, rs);
     if (!rc && R.strs) {
         c->path_stats.paths += rs.ps.n;
         c->path_stats.bytes += rs.ps.offsets()[rs.ps.n];
         c->path_stats.host_paths += rs.ps.n_host;
+    }
+    if (!rc && R.vals) {
+        c->value_stats.paths += rs.pv.n;
+        c->value_stats.bytes += rs.pv.offsets()[2 * rs.pv.n];
+        c->value_stats.host_paths += rs.pv.n_host;
     }
     if (rc) s->broken = true;
     if (!rc && s->pair_mode)  // kept for gpudiff_write_plan_get
@@ -1295,6 +1474,7 @@ int dstore_submit(gpudiff_ctx* c, DStore* s, const gpudiff_event* ev, size_t n, 
     R.links_off = B.links_off();
     R.bound = B.bound;
     R.strs = strs;
+    R.vals = (c->flags & GPUDIFF_OPT_PATH_VALUES) != 0;
     R.space_idx = s->cur;
     R.ticket = *ticket;
     R.outstanding = true;
@@ -1435,7 +1615,7 @@ void dstore_free(gpudiff_ctx* c, DStore* s) {
         if (R.d) gpudiff_dbatch_free(c, R.d);
         if (R.ticket) c->finishers.erase(R.ticket);
         for (void* p : {(void*)R.djson, (void*)R.dmeta, (void*)R.douts, (void*)R.dcoll, (void*)R.ddef, (void*)R.dcnt,
-                        (void*)R.dntab, (void*)R.ps_len, (void*)R.ps_tiles, (void*)R.ps_ctr, (void*)R.ps_out,
+                        (void*)R.dntab, (void*)R.ps_len, (void*)R.ps_tiles, (void*)R.tx_ctr, (void*)R.ps_out,
                         (void*)R.pl_flags, (void*)R.pl_patch, (void*)R.pl_words, (void*)R.pl_tiles, (void*)R.pl_rec,
                         (void*)R.pl_head, (void*)R.pl_wdoc, (void*)R.pl_lens, (void*)R.pl_tdocs, (void*)R.pl_touts,
                         (void*)R.pl_scratch, (void*)R.pl_arena, (void*)R.pl_bytes, (void*)R.pl_mv,
@@ -1443,6 +1623,7 @@ void dstore_free(gpudiff_ctx* c, DStore* s) {
             if (p) (void)hipFree(p);
         for (auto& e : R.ps_ev)
             if (e) (void)hipEventDestroy(e);
+        R.vb.free_all();
         for (auto& e : R.pl_ev)
             if (e) (void)hipEventDestroy(e);
         for (void* p : {(void*)R.hjson, (void*)R.hmeta})
@@ -1455,6 +1636,7 @@ void dstore_free(gpudiff_ctx* c, DStore* s) {
             if (e) (void)hipEventDestroy(e);
     }
     if (s->res_d) gpudiff_dbatch_free(c, s->res_d);
+    s->res_vb.free_all();
     for (hipStream_t* k : {&s->ks, &s->ks0})
         if (*k) {
             (void)hipStreamSynchronize(*k);

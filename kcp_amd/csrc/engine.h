@@ -154,12 +154,52 @@ struct PathStrs {
     std::string tail;
 };
 
+// GPUDIFF_OPT_PATH_VALUES: the changed leaves' old and new values as JSON text, texts 2i / 2i + 1 for hashes[i] /
+// kinds[i].  One allocation, as it comes back from the device in one copy: offsets[2n + 1], the tags[2n] (padded to
+// 8), then the texts' bytes
+struct PathVals {
+    bool on = false;
+    size_t n = 0;  // entries (two texts each)
+    std::vector<uint64_t> words;
+    size_t n_host = 0, n_unresolved = 0;
+    static size_t tag_words(size_t n) { return (2 * n + 7) / 8; }
+    const uint64_t* offsets() const { return words.data(); }
+    const uint8_t* tags() const { return (const uint8_t*)(words.data() + 2 * n + 1); }
+    const char* bytes() const { return (const char*)(words.data() + 2 * n + 1 + tag_words(n)); }
+    // built entry by entry (the host resolution's merge)
+    void begin() {
+        offs.assign(1, 0);
+        tg.clear();
+        tail.clear();
+        n = 0;
+    }
+    void push(uint8_t tag, const char* p, size_t len) {  // one text; two of them make an entry
+        tail.append(p, len);
+        offs.push_back(tail.size());
+        tg.push_back(tag);
+    }
+    void finish() {
+        n = tg.size() / 2;
+        words.assign(2 * n + 1 + tag_words(n) + (tail.size() + 7) / 8, 0);
+        memcpy(words.data(), offs.data(), offs.size() * 8);
+        if (!tg.empty()) memcpy(words.data() + 2 * n + 1, tg.data(), tg.size());
+        if (!tail.empty()) memcpy(words.data() + 2 * n + 1 + tag_words(n), tail.data(), tail.size());
+        offs = {};
+        tg = {};
+        tail = {};
+    }
+    std::vector<uint64_t> offs;
+    std::vector<uint8_t> tg;
+    std::string tail;
+};
+
 struct ResultStore {
     std::vector<uint8_t> flags;
     std::vector<uint32_t> spec, status, dirty, off;
     std::vector<uint64_t> hashes;
     std::vector<uint8_t> kinds;
     PathStrs ps;
+    PathVals pv;
 };
 
 struct gpudiff_ctx {
@@ -187,6 +227,8 @@ struct gpudiff_ctx {
     // GPUDIFF_OPT_DEVICE_ENCODE: gpudiff_submit's pairs go through K0 (dstore.cpp, pair mode)
     DStore* pair_store = nullptr;
     gpudiff_path_stats path_stats{};  // GPUDIFF_OPT_PATH_STRINGS: what the finishers rendered
+    gpudiff_path_stats value_stats{};  // GPUDIFF_OPT_PATH_VALUES: the same, counted for the values
+    uint64_t render_syncs = 0;  // stream synchronisations of the finishers' text rendering (gpudiff_render_syncs_get)
     // submit ring
     gpudiff_dbatch* ring[2] = {nullptr, nullptr};
     gpudiff_hbatch* ring_hb[2] = {nullptr, nullptr};

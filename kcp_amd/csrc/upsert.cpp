@@ -111,6 +111,21 @@ void put_float(std::string& o, double f) {
     }
 }
 
+}  // namespace
+
+// put_float for the value renderer (valstr.h's host formatter, devenc.cpp): Go's text of `f` into out (32 bytes
+// hold any float64: 24 digits and zeros, sign, "0."), its length returned
+namespace gd {
+uint32_t go_float_text(double f, char* out) {
+    std::string s;
+    put_float(s, f);
+    memcpy(out, s.data(), std::min<size_t>(s.size(), 32));
+    return (uint32_t)s.size();
+}
+}  // namespace gd
+
+namespace {
+
 const Member* find(const Node& obj, const char* k) {
     const size_t kl = strlen(k);
     for (uint32_t i = 0; i < obj.n; i++)

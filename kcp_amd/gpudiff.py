@@ -26,9 +26,15 @@ E_INVAL, E_NOMEM, E_DEVICE, E_NODEVICE, E_CAPACITY, E_STATE, E_DECODE, E_NOTFOUN
 SPEC_DIRTY, STATUS_DIRTY, DECODE_ERROR, SPEC_NOOP, STATUS_NOOP = 0x1, 0x2, 0x4, 0x8, 0x10
 PATH_CHANGED, PATH_ADDED, PATH_REMOVED, PATH_STATUS_ABSENT = 0, 1, 2, 3
 PATH_REGION_STATUS = 0x80
+# value type tags (gpudiff_format.h GPUDIFF_TAG_*) and the tag of a value that is not there (GPUDIFF_VALUE_ABSENT)
+TAG_NULL, TAG_FALSE, TAG_TRUE, TAG_INT, TAG_FLOAT, TAG_STR, TAG_EOBJ, TAG_EARR = range(8)
+VALUE_ABSENT = 0xFF
 OPT_TIMING = 0x1
 OPT_DEVICE_ENCODE = 0x2000000
 OPT_PATH_STRINGS = 0x8000000  # device-encoded batches: K15/K16 render the changed paths as text (DiffResult.path_strings)
+# device-encoded batches: K21/K22 render every changed leaf's old and new value as JSON text
+# (DiffResult.path_values)
+OPT_PATH_VALUES = 0x80000000
 OPT_ARENA_SHIFT = 21  # test hook: 4 bits, the K2 wave arenas shrunk 2^k-fold (forces the deferred K4 path)
 OPT_SMALL_PASS = 0x20000000  # a pass of 1..SMALL_PASS_MAX_PAIRS pairs runs as one kernel (K20) with one read-back
 SMALL_PASS_MAX_PAIRS = 4096  # GPUDIFF_SMALL_PASS_MAX_PAIRS
@@ -280,6 +286,11 @@ class PathStringsC(C.Structure):
                 ("n_unresolved", C.c_size_t)]
 
 
+class PathValuesC(C.Structure):
+    _fields_ = [("n_paths", C.c_size_t), ("offsets", C.c_void_p), ("bytes", C.c_void_p), ("tags", C.c_void_p),
+                ("n_host", C.c_size_t), ("n_unresolved", C.c_size_t)]
+
+
 class PathStats(C.Structure):
     _fields_ = [("batches", C.c_uint64), ("paths", C.c_uint64), ("bytes", C.c_uint64), ("host_paths", C.c_uint64),
                 ("kernel_ms", C.c_double), ("timed_batches", C.c_uint64)]
@@ -341,6 +352,11 @@ SIGNATURES = [
     ("gpudiff_result_release", None, [_P, C.POINTER(Result)]),
     ("gpudiff_result_path_strings", C.c_int, [_P, C.POINTER(Result), C.POINTER(PathStringsC)]),
     ("gpudiff_path_strings_stats_get", C.c_int, [_P, C.POINTER(PathStats)]),
+    ("gpudiff_result_path_values", C.c_int, [_P, C.POINTER(Result), C.POINTER(PathValuesC)]),
+    ("gpudiff_path_values_stats_get", C.c_int, [_P, C.POINTER(PathStats)]),
+    ("gpudiff_render_syncs_get", C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    ("gpudiff_render_value_from_blob", C.c_int, [C.c_char_p, C.POINTER(ObjInfo), C.c_uint32, C.c_uint64,
+                                                 C.POINTER(C.c_uint8), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("gpudiff_last_timings", C.c_int, [_P, C.POINTER(Timings)]),
     ("gpudiff_pass_stats_get", C.c_int, [_P, C.POINTER(PassStats)]),
     ("gpudiff_sync", C.c_int, [_P]),
@@ -512,6 +528,12 @@ class DiffResult:
     path_strings: Optional[List[bytes]] = None
     paths_host: int = 0             # entries the host path rendered (K0's deferrals)
     paths_unresolved: int = 0       # entries whose table walk failed (empty strings); always 0
+    # OPT_PATH_VALUES on a device-encoded batch: per changed path (old_tag, old_text | None, new_tag, new_text | None),
+    # the JSON text of A's and B's leaf (VALUE_ABSENT / None where the side has none); None when the engine rendered
+    # none (gpudiff_result_path_values: E_STATE)
+    path_values: Optional[List[Tuple[int, Optional[bytes], int, Optional[bytes]]]] = None
+    values_host: int = 0            # entries whose pair the host resolved (K0's deferrals)
+    values_unresolved: int = 0      # values whose leaf was not found (ABSENT); always 0
 
     def paths_of(self, k: int) -> List[Tuple[int, int]]:
         """[(hash, kind)] of the k-th dirty pair."""
@@ -526,6 +548,18 @@ class DiffResult:
         b, e = int(self.path_offsets[k]), int(self.path_offsets[k + 1])
         return [(h, kd, s.decode("utf-8", "surrogateescape")) for h, kd, s in
                 zip(self.path_hashes[b:e].tolist(), self.path_kinds[b:e].tolist(), self.path_strings[b:e])]
+
+
+def _changed_values_of(self, k: int):
+    """[(hash, kind, old_tag, old_text | None, new_tag, new_text | None)] of the k-th dirty pair (OPT_PATH_VALUES)."""
+    if self.path_values is None:
+        raise GpuDiffError(E_STATE, "DiffResult.changed_values_of")
+    b, e = int(self.path_offsets[k]), int(self.path_offsets[k + 1])
+    return [(h, kd) + v for h, kd, v in
+            zip(self.path_hashes[b:e].tolist(), self.path_kinds[b:e].tolist(), self.path_values[b:e])]
+
+
+DiffResult.changed_values_of = _changed_values_of
 
 
 def _arr(ptr, n, dtype):
@@ -872,6 +906,18 @@ class Engine:
                 out.paths_host, out.paths_unresolved = int(ps.n_host), int(ps.n_unresolved)
             elif rc != E_STATE:
                 raise GpuDiffError(rc, "gpudiff_result_path_strings")
+            pv = PathValuesC()
+            rc = _lib.gpudiff_result_path_values(self.ctx, C.byref(r), C.byref(pv))
+            if rc == OK:
+                offs = _arr(pv.offsets, 2 * pv.n_paths + 1, np.uint64).tolist()
+                tags = _arr(pv.tags, 2 * pv.n_paths, np.uint8).tolist()
+                raw = C.string_at(pv.bytes, offs[-1]) if offs[-1] else b""
+                txt = [None if tags[t] == VALUE_ABSENT else raw[offs[t]:offs[t + 1]] for t in range(2 * pv.n_paths)]
+                out.path_values = [(tags[2 * i], txt[2 * i], tags[2 * i + 1], txt[2 * i + 1])
+                                   for i in range(pv.n_paths)]
+                out.values_host, out.values_unresolved = int(pv.n_host), int(pv.n_unresolved)
+            elif rc != E_STATE:
+                raise GpuDiffError(rc, "gpudiff_result_path_values")
         finally:
             _lib.gpudiff_result_release(self.ctx, C.byref(r))
         return out
@@ -881,6 +927,18 @@ class Engine:
         st = PathStats()
         _chk(_lib.gpudiff_path_strings_stats_get(self.ctx, C.byref(st)), "gpudiff_path_strings_stats_get")
         return st
+
+    def path_values_stats(self) -> PathStats:
+        """gpudiff_path_values_stats_get: what OPT_PATH_VALUES rendered so far (kernel_ms with timing)."""
+        st = PathStats()
+        _chk(_lib.gpudiff_path_values_stats_get(self.ctx, C.byref(st)), "gpudiff_path_values_stats_get")
+        return st
+
+    def render_syncs(self) -> int:
+        """gpudiff_render_syncs_get: stream synchronisations spent on rendering paths and values as text."""
+        n = C.c_uint64(0)
+        _chk(_lib.gpudiff_render_syncs_get(self.ctx, C.byref(n)), "gpudiff_render_syncs_get")
+        return int(n.value)
 
     def pass_stats(self) -> PassStats:
         """gpudiff_pass_stats_get: passes, fused small passes, the ones redone (by reason), read-back rounds."""
@@ -1347,6 +1405,32 @@ def render_path_from_blob(blob: bytes, info, seed: int, path_hash: int) -> bytes
     _chk(_lib.gpudiff_render_path_from_blob(blob, C.byref(info), seed, path_hash, C.cast(buf, C.c_void_p), n.value,
                                             C.byref(n)), "gpudiff_render_path_from_blob")
     return buf.raw[:n.value]
+
+
+def render_value_from_blob(blob: bytes, info, status_region: bool, path_hash: int, cap: Optional[int] = None):
+    """gpudiff_render_value_from_blob: (tag, JSON text) of the leaf `path_hash` names in the blob's spec or status
+    segment (encode_object_host / Engine.encode_objects output; info = its dict or ObjInfo).  No GPU needed.
+    cap: the buffer to offer (default: sized by a first call); a text longer than it raises E_CAPACITY with the
+    needed length as the error's `needed`."""
+    if not isinstance(info, ObjInfo):
+        d, info = info, ObjInfo()
+        for f, _ in ObjInfo._fields_:
+            setattr(info, f, d.get(f, 0))
+    n, tag = C.c_size_t(0), C.c_uint8(0)
+    if cap is None:
+        rc = _lib.gpudiff_render_value_from_blob(blob, C.byref(info), int(bool(status_region)), path_hash,
+                                                 C.byref(tag), None, 0, C.byref(n))
+        if rc != E_CAPACITY:  # a present text is never empty
+            raise GpuDiffError(rc, "gpudiff_render_value_from_blob")
+        cap = n.value
+    buf = C.create_string_buffer(max(1, cap))
+    rc = _lib.gpudiff_render_value_from_blob(blob, C.byref(info), int(bool(status_region)), path_hash, C.byref(tag),
+                                             C.cast(buf, C.c_void_p), cap, C.byref(n))
+    if rc != OK:
+        err = GpuDiffError(rc, "gpudiff_render_value_from_blob")
+        err.needed = int(n.value)
+        raise err
+    return int(tag.value), buf.raw[:n.value]
 
 
 def encode_object_host(doc, seed: int = 0, path_hash_bits: int = PATH_HASH_BITS):
