@@ -97,11 +97,13 @@ enum {
 
 /* context option flags (any other bit: gpudiff_open returns GPUDIFF_E_INVAL).  Round 5 removed the A/B tuning
  * bits of earlier rounds whose measurements rejected them (DESIGN.md §5-§6 keep the numbers):
- * 0x2 two upload streams, 0x4 index-order final round, 0x8 pipelined K4 join, 0x10-0x80 tail shapes, bits 9-20
+ * 0x2 two upload streams, 0x4 index-order final round, 0x8 pipelined K4 join, 0x10-0x80 tail shapes (0x40 has a new meaning below), bits 9-20
  * kernel variants / blocks per CU / segmented passes, bits 26-31 K0 occupancy, items per wave, deep-join bounds.
  * ABI 6 retired 0x100 (ABI 5's K2 timeline bit, ABI 4's K2 variant bit): refused like the rest, so no caller of
  * either meaning gets the other; the timeline build is selected by gpudiff_k2_profile. */
 #define GPUDIFF_OPT_TIMING 0x1u          /* record per-kernel HIP event times (gpudiff_last_timings) */
+#define GPUDIFF_OPT_K2_ROWS 0x40u        /* diagnostic (the A/B, the tests): K2 reads the 64-B rows although the
+                                            batch's 16-B pair descriptors are current; results do not change */
 #define GPUDIFF_OPT_ARENA_SHIFT 21u      /* 4 bits, test hook: shrink the per-wave path arena 2^k-fold (forces
                                             pairs through the deferred K4 path) */
 #define GPUDIFF_OPT_DEVICE_ENCODE 0x2000000u /* gpudiff_submit / single-pair helpers: raw JSON up, kernel K0
@@ -119,7 +121,7 @@ enum {
                                                 inside gpudiff_wait (gpudiff_result_path_values) */
 #define GPUDIFF_OPT_KNOWN                                                                                         \
     (GPUDIFF_OPT_TIMING | (0xFu << GPUDIFF_OPT_ARENA_SHIFT) | GPUDIFF_OPT_DEVICE_ENCODE | GPUDIFF_OPT_PATH_STRINGS | \
-     GPUDIFF_OPT_SMALL_PASS | GPUDIFF_OPT_PATH_VALUES)
+     GPUDIFF_OPT_SMALL_PASS | GPUDIFF_OPT_PATH_VALUES | GPUDIFF_OPT_K2_ROWS)
 
 /* GPUDIFF_OPT_SMALL_PASS: the largest pass the fused kernel takes (64 chunks of 64 pairs: its finishing block scans
  * the chunks with one lane each), and the most changed paths it finishes itself -- a pass with more is run again as

@@ -153,6 +153,118 @@ GPUDIFF_HD static inline uint64_t gpudiff_pair_compare_bytes(const gpudiff_pair_
     return sizeof(gpudiff_pair_row) + 1u + 2u * per;
 }
 
+/* ---- the pair descriptor: 16 bytes that stand for a row in the decision kernel's stream (DESIGN.md §5
+ * "Pair descriptors").  Written beside the rows when a batch is appended; K2 reads it instead of the 64-B row and
+ * goes back to the row only for what the descriptor leaves out (the leaf counts, the seed's value, the IDs).
+ *
+ *   word 0, 1   off_a >> 7, off_b >> 7                  (blobs are GPUDIFF_BLOB_ALIGN aligned)
+ *   bits  0-18  spec segment bytes of A, in 16-B units  (word 2 | word 3 << 32)
+ *   bits 19-37  spec segment bytes of B, in 16-B units
+ *   bits 38-56  status segment bytes of A, in 16-B units
+ *   bits 57-63  GPUDIFF_PD_* >> 0
+ *
+ * Two of the bits cannot be derived from the sizes: SPEC_EQ and STAT_EQ mean that the leaf counts and the arenas
+ * are both equal, which equal segment bytes do not imply (16 L + arena coincides for other L).
+ *
+ * A row whose offsets or sizes do not fit, or are not multiples of the units, or whose status leaf counts
+ * contradict its NO_STAT bit (never an encoder's row), is packed as the escape: all ones.  No packed row equals it
+ * -- it would carry NO_STAT with a non-zero status segment -- and word 3 alone tells. */
+#define GPUDIFF_PD_ERR 0x01u       /* either side failed to decode */
+#define GPUDIFF_PD_SPEC_EQ 0x02u   /* spec_l and spec_ar equal on both sides */
+#define GPUDIFF_PD_STAT_EQ 0x04u   /* stat_l and stat_ar equal on both sides */
+#define GPUDIFF_PD_HAS_ST_B 0x08u  /* flags_b & GPUDIFF_OBJ_HAS_STATUS */
+#define GPUDIFF_PD_HAS_ST_A 0x10u  /* flags_a & GPUDIFF_OBJ_HAS_STATUS */
+#define GPUDIFF_PD_SEED 0x20u      /* the pair's path-hash seed != 0 */
+#define GPUDIFF_PD_NO_STAT 0x40u   /* stat_l and stat_ar zero on both sides */
+#define GPUDIFF_PD_SIZE_BITS 19u
+#define GPUDIFF_PD_SIZE_MAX 0x7FFFFu  /* 16-B units: segments below 8 MiB */
+#define GPUDIFF_PD_ESCAPE 0xFFFFFFFFu
+
+typedef struct gpudiff_pair_desc {
+    uint32_t w[4];
+} gpudiff_pair_desc;
+
+/* what K2's stream needs of a pair: n1 spec chunks from off, n2 status chunks from off + 16 n1 + adj (per side),
+ * and the GPUDIFF_PD_* bits its decisions read */
+typedef struct gpudiff_pair_geom {
+    uint64_t off_a, off_b;
+    uint32_t n1, n2, adj_a, adj_b;
+    uint32_t bits;
+} gpudiff_pair_geom;
+
+/* the stream's chunk counts from the segment bytes and the bits: K2's rule (gpudiff_pair_compare_bytes counts the
+ * same chunks) */
+GPUDIFF_HD static inline gpudiff_pair_geom gpudiff_pair_geom_of(uint64_t off_a, uint64_t off_b, uint32_t seg_a,
+                                                                uint32_t seg_b, uint32_t seg_t, uint32_t bits) {
+    gpudiff_pair_geom g;
+    const int ok = !(bits & GPUDIFF_PD_ERR);
+    const int spec_sz = (bits & GPUDIFF_PD_SPEC_EQ) != 0u;
+    const int stat_sz = (bits & GPUDIFF_PD_HAS_ST_B) && (bits & GPUDIFF_PD_STAT_EQ);
+    const uint32_t r128 = (seg_a + seg_t + 127u) & ~127u;
+    g.off_a = off_a;
+    g.off_b = off_b;
+    g.n1 = (ok && spec_sz) ? ((!stat_sz && (bits & GPUDIFF_PD_NO_STAT)) ? ((seg_a + 127u) & ~127u) : seg_a) >> 4 : 0u;
+    g.n2 = (ok && stat_sz) ? (spec_sz ? r128 - seg_a : seg_t) >> 4 : 0u;
+    g.adj_a = seg_a - 16u * g.n1;
+    g.adj_b = seg_b - 16u * g.n1;
+    g.bits = bits;
+    return g;
+}
+
+GPUDIFF_HD static inline uint32_t gpudiff_pair_row_bits(const gpudiff_pair_row* r) {
+    return (((r->flags_a | r->flags_b) & GPUDIFF_OBJ_DECODE_ERR) ? GPUDIFF_PD_ERR : 0u) |
+           ((r->spec_l_a == r->spec_l_b && r->spec_ar_a == r->spec_ar_b) ? GPUDIFF_PD_SPEC_EQ : 0u) |
+           ((r->stat_l_a == r->stat_l_b && r->stat_ar_a == r->stat_ar_b) ? GPUDIFF_PD_STAT_EQ : 0u) |
+           ((r->flags_b & GPUDIFF_OBJ_HAS_STATUS) ? GPUDIFF_PD_HAS_ST_B : 0u) |
+           ((r->flags_a & GPUDIFF_OBJ_HAS_STATUS) ? GPUDIFF_PD_HAS_ST_A : 0u) |
+           (((r->flags_a >> GPUDIFF_OBJ_SEED_SHIFT) & 0xFFu) ? GPUDIFF_PD_SEED : 0u) |
+           ((r->stat_l_a | r->stat_l_b | r->stat_ar_a | r->stat_ar_b) == 0u ? GPUDIFF_PD_NO_STAT : 0u);
+}
+
+/* the same from the row itself (an escape's lane in K2) */
+GPUDIFF_HD static inline gpudiff_pair_geom gpudiff_pair_row_geom(const gpudiff_pair_row* r) {
+    return gpudiff_pair_geom_of(r->off_a, r->off_b, (uint32_t)gpudiff_seg_bytes(r->spec_l_a, r->spec_ar_a),
+                                (uint32_t)gpudiff_seg_bytes(r->spec_l_b, r->spec_ar_b),
+                                (uint32_t)gpudiff_seg_bytes(r->stat_l_a, r->stat_ar_a), gpudiff_pair_row_bits(r));
+}
+
+GPUDIFF_HD static inline gpudiff_pair_desc gpudiff_pair_desc_pack(const gpudiff_pair_row* r) {
+    gpudiff_pair_desc d;
+    const uint64_t sa = gpudiff_seg_bytes(r->spec_l_a, r->spec_ar_a), sb = gpudiff_seg_bytes(r->spec_l_b, r->spec_ar_b);
+    const uint64_t st = gpudiff_seg_bytes(r->stat_l_a, r->stat_ar_a);
+    const uint32_t bits = gpudiff_pair_row_bits(r);
+    const uint64_t size_max = (uint64_t)GPUDIFF_PD_SIZE_MAX << 4;
+    const int fits = ((r->off_a | r->off_b) & (GPUDIFF_BLOB_ALIGN - 1u)) == 0u && (r->off_a >> 7) <= 0xFFFFFFFFull &&
+                     (r->off_b >> 7) <= 0xFFFFFFFFull && ((sa | sb | st) & 15u) == 0u && sa <= size_max &&
+                     sb <= size_max && st <= size_max &&
+                     /* K2 joins the status region when stat_l_a + stat_l_b != 0 (u32): the NO_STAT bit must say so */
+                     ((uint32_t)(r->stat_l_a + r->stat_l_b) == 0u) == ((bits & GPUDIFF_PD_NO_STAT) != 0u);
+    if (!fits) {
+        d.w[0] = d.w[1] = d.w[2] = d.w[3] = GPUDIFF_PD_ESCAPE;
+        return d;
+    }
+    {
+        const uint64_t zw = (sa >> 4) | ((sb >> 4) << GPUDIFF_PD_SIZE_BITS) | ((st >> 4) << (2u * GPUDIFF_PD_SIZE_BITS)) |
+                            ((uint64_t)bits << (3u * GPUDIFF_PD_SIZE_BITS));
+        d.w[0] = (uint32_t)(r->off_a >> 7);
+        d.w[1] = (uint32_t)(r->off_b >> 7);
+        d.w[2] = (uint32_t)zw;
+        d.w[3] = (uint32_t)(zw >> 32);
+    }
+    return d;
+}
+
+GPUDIFF_HD static inline int gpudiff_pair_desc_is_escape(uint32_t w3) { return w3 == GPUDIFF_PD_ESCAPE; }
+
+/* of a descriptor that is not the escape */
+GPUDIFF_HD static inline gpudiff_pair_geom gpudiff_pair_desc_unpack(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3) {
+    const uint64_t zw = ((uint64_t)w3 << 32) | w2;
+    return gpudiff_pair_geom_of((uint64_t)w0 << 7, (uint64_t)w1 << 7, (w2 & GPUDIFF_PD_SIZE_MAX) << 4,
+                                ((uint32_t)(zw >> GPUDIFF_PD_SIZE_BITS) & GPUDIFF_PD_SIZE_MAX) << 4,
+                                ((w3 >> (2u * GPUDIFF_PD_SIZE_BITS - 32u)) & GPUDIFF_PD_SIZE_MAX) << 4,
+                                w3 >> (3u * GPUDIFF_PD_SIZE_BITS - 32u));
+}
+
 GPUDIFF_HD static inline uint32_t gpudiff_meta(uint32_t tag, uint32_t len) { return (len << 3) | tag; }
 GPUDIFF_HD static inline uint32_t gpudiff_meta_tag(uint32_t m) { return m & 7u; }
 GPUDIFF_HD static inline uint32_t gpudiff_meta_len(uint32_t m) { return m >> 3; }

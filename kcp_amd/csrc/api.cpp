@@ -80,6 +80,7 @@ static int ensure_paths(gpudiff_dbatch* d, uint64_t arena, uint64_t scratch) {
 static DiffBuffers buffers_of(gpudiff_ctx* c, gpudiff_dbatch* d) {
     DiffBuffers b;
     b.rows = d->rows;
+    b.desc = (d->desc_gen == d->rows_gen && !(c->flags & GPUDIFF_OPT_K2_ROWS)) ? d->desc : nullptr;
     b.pool = d->pool;
     b.pair_ids = d->pair_ids;
     b.n_pairs = (uint32_t)d->n_pairs;
@@ -387,7 +388,7 @@ int gpudiff_dbatch_create(gpudiff_ctx* c, uint64_t pool_bytes, uint64_t max_pair
     d->device = c->device;
     const uint64_t np = std::max<uint64_t>(max_pairs, 1);
     if ((rc = dalloc(&d->pool, d->pool_cap)) || (rc = dalloc(&d->rows, np)) || (rc = dalloc(&d->pair_ids, np)) ||
-        (rc = alloc_outputs(d.get()))) {
+        (rc = dalloc(&d->desc, np)) || (rc = alloc_outputs(d.get()))) {
         dfree_all(d.get());
         return rc;
     }
@@ -432,6 +433,8 @@ static void view_sync(gpudiff_dbatch* d) {
     d->value_bytes = b->value_bytes;
     d->size_hint_bytes = b->size_hint_bytes;
     d->rows_gen = b->rows_gen;
+    d->desc = b->desc;
+    d->desc_gen = b->desc_gen;
 }
 
 // every per-pass output of a batch (a view has only these)
@@ -470,7 +473,7 @@ int gpudiff_dbatch_append(gpudiff_ctx* c, gpudiff_dbatch* d, const gpudiff_hbatc
     HIPCHK(hipMemcpyAsync(d->rows + begin, hb->rows, hb->n * sizeof(gpudiff_pair_row), hipMemcpyHostToDevice,
                           c->stream));
     if (hb->used) HIPCHK(hipEventRecord(hb->used, c->stream));
-    HIPCHK(launch_rebase(c->stream, d->rows, begin, end, base, d->pair_ids));
+    HIPCHK(launch_rebase(c->stream, d->rows, begin, end, base, d->pair_ids, d->desc));
     uint64_t cb = 0, vb = 0;
     for (size_t i = 0; i < hb->n; i++) {
         const gpudiff_pair_row& r = hb->rows[i];
@@ -483,7 +486,10 @@ int gpudiff_dbatch_append(gpudiff_ctx* c, gpudiff_dbatch* d, const gpudiff_hbatc
     d->value_bytes += vb;
     d->pool_used += hb->pool_bytes;
     d->n_pairs = end;
+    // the descriptors stay current when those of the rows before this append were (or there are none)
+    const bool desc_current = begin == 0 || d->desc_gen == d->rows_gen;
     d->rows_gen++;
+    d->desc_gen = desc_current ? d->rows_gen : ~0ull;
     d->leaves += hb->leaves;
     return GPUDIFF_OK;
 }

@@ -116,6 +116,11 @@ struct gpudiff_dbatch {
     uint32_t* tail_perm = nullptr;  // K2's largest-first final round (kernels.h DiffBuffers)
     gd::TailPermKey tail_perm_key;
     uint64_t rows_gen = 0;  // bumped whenever the rows change (appends, resets, store batches): K2's cached order
+    // K2's 16-B pair descriptors (gpudiff_format.h), parallel to rows; a view borrows its base's.  Written by
+    // gpudiff_dbatch_append's rebase kernel only: desc_gen == rows_gen says every resident row's descriptor is
+    // current, and K2 gets the array only then -- any other producer of rows bumps rows_gen alone and K2 reads rows
+    uint4* desc = nullptr;
+    uint64_t desc_gen = ~0ull;
     // GPUDIFF_OPT_SMALL_PASS: the result image K20 packs (small_pass.h; allocated by the batch's first small pass),
     // and whether the pass `done` stands for was a small one (collect_results reads the image then)
     uint8_t* small_image = nullptr;
@@ -259,8 +264,8 @@ inline int dalloc(T** p, uint64_t count) {
 
 inline void dfree_all(gpudiff_dbatch* d) {
     if (d->pool && !d->pool_borrowed) (void)hipFree(d->pool);
-    if (d->base) d->rows = nullptr, d->pair_ids = nullptr;  // a view's inputs are its base's
-    void* ps[] = {d->rows, d->pair_ids, d->flags, d->caps, d->chunk_counts, d->summary, d->spec_ids,
+    if (d->base) d->rows = nullptr, d->pair_ids = nullptr, d->desc = nullptr;  // a view's inputs are its base's
+    void* ps[] = {d->rows, d->pair_ids, d->desc, d->flags, d->caps, d->chunk_counts, d->summary, d->spec_ids,
                   d->status_ids, d->dirty_ids, d->dirty_idx, d->scratch_off, d->path_count, d->path_off,
                   d->tile_sums, d->path_src, d->path_cnt, d->arena_h, d->arena_k,
                   d->scratch_h, d->scratch_k, d->out_h, d->out_k, d->nbits, d->noop_d, d->slot_owner,

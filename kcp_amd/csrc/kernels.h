@@ -17,6 +17,7 @@ constexpr uint64_t kMaxScratchEntries = 1ull << 31;
 // 2 n_dirty, 3 K4 scratch entries (saturating), 4 overflow, 5 n_paths, 6 any pair deferred to K4, 7 -.
 struct DiffBuffers {
     const gpudiff_pair_row* rows;
+    const uint4* desc;  // the rows' 16-B descriptors (gpudiff_format.h), or nullptr: stale, or switched off
     const uint8_t* pool;
     const uint32_t* pair_ids;
     uint32_t n_pairs;
@@ -80,8 +81,9 @@ constexpr uint32_t kK2TailQuarters = 2;
 // waves of a K2 launch over nchunks 64-pair chunks (sizes the wave arenas)
 uint32_t k2_grid_waves(const DiffBuffers& b, uint32_t nchunks);
 
+// rows [begin, end): offsets += base, pair_ids[i] = the row's; desc != nullptr: their K2 descriptors too
 hipError_t launch_rebase(hipStream_t s, gpudiff_pair_row* rows, uint32_t begin, uint32_t end, uint64_t base,
-                         uint32_t* pair_ids);
+                         uint32_t* pair_ids, uint4* desc);
 // object-store compaction: blob copies between the two spaces
 struct BlobMove {
     uint64_t src, dst, bytes;

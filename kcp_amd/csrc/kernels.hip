@@ -704,7 +704,11 @@ __device__ __forceinline__ uint32_t lds_add(uint32_t* p, uint32_t v) {
     return __hip_atomic_fetch_add(p, v, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
-template <int U, int MINB, bool PROF = false, bool HELP = false>
+// DESC (the default kernel and its timeline build): an item's lanes read their pairs' 16-B descriptors (desc,
+// gpudiff_format.h) instead of the 64-B rows.  A lane loads its row only when its descriptor is the escape (before
+// the stream) or when its pair turns out dirty in any way but the status-absent sentinel under seed 0 (after it: the
+// leaf counts behind the K4 cap and the seed's value are not in the descriptor).
+template <int U, int MINB, bool PROF = false, bool HELP = false, bool DESC = false>
 __global__ __launch_bounds__(256, MINB) void k_compare_flat(const gpudiff_pair_row* __restrict__ rows,
                                                       const uint8_t* __restrict__ pool, uint32_t n,
                                                       uint8_t* __restrict__ flags, uint32_t* __restrict__ caps,
@@ -715,7 +719,9 @@ __global__ __launch_bounds__(256, MINB) void k_compare_flat(const gpudiff_pair_r
                                                       uint32_t* __restrict__ path_src, uint32_t* __restrict__ path_cnt,
                                                       uint8_t* __restrict__ nbits, uint64_t mask,
                                                       uint32_t* __restrict__ summary, uint32_t sub_arg,
-                                                      const uint32_t* __restrict__ tail_perm) {
+                                                      const uint32_t* __restrict__ tail_perm,
+                                                      const uint4* __restrict__ desc) {
+    static_assert(!(DESC && HELP), "the deep-pair kernels keep the rows");
     const uint32_t lane = lane_id();
     const uint32_t wave = uni((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
     const uint32_t nwaves = (gridDim.x * blockDim.x) >> 6;
@@ -888,7 +894,10 @@ __global__ __launch_bounds__(256, MINB) void k_compare_flat(const gpudiff_pair_r
         const bool valid = lane < cnt;
         // ---- rows: lane k holds pair p0 + k
         u32x4 v0 = {0, 0, 0, 0}, v1 = v0, v2 = v0, v3 = v0;
-        if (valid) {
+        [[maybe_unused]] u32x4 dv = v0;  // DESC: the pair's descriptor
+        if constexpr (DESC) {
+            if (valid) dv = *(const u32x4*)(desc + p0 + lane);
+        } else if (valid) {
             const u32x4* rp = (const u32x4*)(rows + p0 + lane);
             v0 = rp[0];  // off_a, off_b
             v1 = rp[1];  // spec_l_a, spec_l_b, spec_ar_a, spec_ar_b
@@ -899,28 +908,53 @@ __global__ __launch_bounds__(256, MINB) void k_compare_flat(const gpudiff_pair_r
             tp_r = wall_clock64();
             tp_rows += tp_r - tp_i;
         }
-        const uint64_t off_a = ((uint64_t)v0.y << 32) | v0.x, off_b = ((uint64_t)v0.w << 32) | v0.z;
-        const bool err = valid && ((v3.x | v3.y) & GPUDIFF_OBJ_DECODE_ERR) != 0u;
-        const bool ok = valid && !err;
-        const bool spec_sz = v1.x == v1.y && v1.z == v1.w;
-        const bool has_st_b = (v3.y & GPUDIFF_OBJ_HAS_STATUS) != 0u;
-        const bool stat_sz = has_st_b && v2.x == v2.y && v2.z == v2.w;
-        const uint32_t seg_a = (uint32_t)seg_bytes(v1.x, v1.z), seg_b = (uint32_t)seg_bytes(v1.y, v1.w);
-        const uint32_t seg_t = (uint32_t)seg_bytes(v2.x, v2.z);
-        // whole 128-B lines wherever both sides' spans are equal: with both regions compared the stream
-        // runs to the body's end (segments + zero pad, gpudiff_blob_body), with spec only and no status
-        // leaves on either side the spec span is padded the same way; a stream that ends inside a line
-        // costs a partial-line request per object (engine.h pair_compare_bytes counts the same chunks)
-        const uint32_t r128 = ((seg_a + seg_t + 127u) & ~127u);
-        const bool no_stat = (v2.x | v2.y | v2.z | v2.w) == 0u;
-        const uint32_t n1 = (ok && spec_sz) ? ((!stat_sz && no_stat) ? ((seg_a + 127u) & ~127u) : seg_a) >> 4 : 0u;
-        const uint32_t n2 = (ok && stat_sz) ? (spec_sz ? r128 - seg_a : seg_t) >> 4 : 0u;
+        uint64_t off_a, off_b;
+        bool err, spec_sz, has_st_b, stat_sz;
+        uint32_t n1, n2, adj_a, adj_b;
+        // DESC: the pair's GPUDIFF_PD_* bits | kPdRow (its descriptor is the escape): all the stream leaves alive
+        [[maybe_unused]] uint32_t dbits = 0;
+        constexpr uint32_t kPdRow = 0x80u;
+        if constexpr (DESC) {
+            // the geometry from the descriptor (gpudiff_pair_desc_unpack: the row's rule below, from 16-B units); an
+            // escape's lane takes it from its row
+            gpudiff_pair_geom g = gpudiff_pair_desc_unpack(dv.x, dv.y, dv.z, dv.w);
+            if (valid && gpudiff_pair_desc_is_escape(dv.w)) {
+                const gpudiff_pair_row r = rows[p0 + lane];
+                g = gpudiff_pair_row_geom(&r);
+                g.bits |= kPdRow;
+            }
+            dbits = g.bits;
+            off_a = g.off_a, off_b = g.off_b;
+            err = valid && (dbits & GPUDIFF_PD_ERR) != 0u;
+            spec_sz = (dbits & GPUDIFF_PD_SPEC_EQ) != 0u;
+            has_st_b = (dbits & GPUDIFF_PD_HAS_ST_B) != 0u;
+            stat_sz = has_st_b && (dbits & GPUDIFF_PD_STAT_EQ) != 0u;
+            n1 = valid ? g.n1 : 0u, n2 = valid ? g.n2 : 0u;
+            adj_a = g.adj_a, adj_b = g.adj_b;
+        } else {
+            off_a = ((uint64_t)v0.y << 32) | v0.x, off_b = ((uint64_t)v0.w << 32) | v0.z;
+            err = valid && ((v3.x | v3.y) & GPUDIFF_OBJ_DECODE_ERR) != 0u;
+            const bool ok = valid && !err;
+            spec_sz = v1.x == v1.y && v1.z == v1.w;
+            has_st_b = (v3.y & GPUDIFF_OBJ_HAS_STATUS) != 0u;
+            stat_sz = has_st_b && v2.x == v2.y && v2.z == v2.w;
+            const uint32_t seg_a = (uint32_t)seg_bytes(v1.x, v1.z), seg_b = (uint32_t)seg_bytes(v1.y, v1.w);
+            const uint32_t seg_t = (uint32_t)seg_bytes(v2.x, v2.z);
+            // whole 128-B lines wherever both sides' spans are equal: with both regions compared the stream
+            // runs to the body's end (segments + zero pad, gpudiff_blob_body), with spec only and no status
+            // leaves on either side the spec span is padded the same way; a stream that ends inside a line
+            // costs a partial-line request per object (engine.h pair_compare_bytes counts the same chunks)
+            const uint32_t r128 = ((seg_a + seg_t + 127u) & ~127u);
+            const bool no_stat = (v2.x | v2.y | v2.z | v2.w) == 0u;
+            n1 = (ok && spec_sz) ? ((!stat_sz && no_stat) ? ((seg_a + 127u) & ~127u) : seg_a) >> 4 : 0u;
+            n2 = (ok && stat_sz) ? (spec_sz ? r128 - seg_a : seg_t) >> 4 : 0u;
+            // chunk k of a pair: spec chunk at off + 16k (k < n1), status chunk at off + seg + 16 (k - n1)
+            adj_a = seg_a - 16u * n1, adj_b = seg_b - 16u * n1;
+        }
         const uint32_t tot = n1 + n2;
         const uint32_t incl = wave_incl_scan(tot);
         const uint32_t total = uni(shfl32(incl, 63));
         const uint32_t first = incl - tot;
-        // chunk k of a pair: spec chunk at off + 16k (k < n1), status chunk at off + seg + 16 (k - n1)
-        const uint32_t adj_a = seg_a - 16u * n1, adj_b = seg_b - 16u * n1;
         uint64_t mis_s = 0, mis_t = 0;  // pairs with a differing spec / status chunk (wave-uniform)
         [[maybe_unused]] uint64_t tp_s0 = 0;
         if constexpr (PROF) {
@@ -971,6 +1005,24 @@ __global__ __launch_bounds__(256, MINB) void k_compare_flat(const gpudiff_pair_r
         if constexpr (PROF) {
             tp_s1 = wall_clock64();
             tp_stream += tp_s1 - tp_s0;
+        }
+        if constexpr (DESC) {
+            // what the decisions read of a row: the leaf counts (v1.xy, v2.xy: a dirty pair's K4 cap) and flags_a
+            // (v3.x: the seed's value).  A dirty pair's lane loads them now -- but not the commonest dirty pair, spec
+            // clean and B without a status key where neither side has status leaves and the seed is 0: its counts
+            // are zero (the cap: the sentinel's one entry) and its flags_a is what the descriptor's bits say, as for
+            // a clean pair (whose flags_a tells seeded or not, never the seed)
+            v3.x = ((dbits & GPUDIFF_PD_HAS_ST_A) ? GPUDIFF_OBJ_HAS_STATUS : 0u) |
+                   ((dbits & GPUDIFF_PD_SEED) ? 1u << GPUDIFF_OBJ_SEED_SHIFT : 0u);
+            const bool sd = !spec_sz || ((mis_s >> lane) & 1ull), td = !stat_sz || ((mis_t >> lane) & 1ull);
+            const bool plain_sent = !sd && !has_st_b && (dbits & GPUDIFF_PD_NO_STAT) && !(dbits & (GPUDIFF_PD_SEED | kPdRow));
+            if (valid && !err && (sd || td) && !plain_sent) {
+                const uint32_t* rp = (const uint32_t*)(rows + p0 + lane);
+                const uint2 ls = *(const uint2*)(rp + 4), lt = *(const uint2*)(rp + 8);
+                v1.x = ls.x, v1.y = ls.y;  // spec_l_a, spec_l_b
+                v2.x = lt.x, v2.y = lt.y;  // stat_l_a, stat_l_b
+                v3.x = rp[12];             // flags_a
+            }
         }
         // ---- decisions (compare_pair's rules)
         uint32_t myflag = 0, mycap = 0, mysrc = 0, mycnt = 0, mynoop = 0;
@@ -1236,13 +1288,23 @@ __global__ __launch_bounds__(256) void k_move_blobs(const uint8_t* __restrict__ 
 }
 
 // ---------------------------------------------------------------- ingest helper
+// ... and, for an appended batch, each row's 16-B descriptor for K2's stream (gpudiff_format.h), from the rebased
+// row: the one place that touches every row anyway (desc == nullptr: the caller's descriptors go stale)
 __global__ __launch_bounds__(256) void k_rebase_rows(gpudiff_pair_row* __restrict__ rows, uint32_t begin, uint32_t end,
-                                                     uint64_t base, uint32_t* __restrict__ pair_ids) {
+                                                     uint64_t base, uint32_t* __restrict__ pair_ids,
+                                                     uint4* __restrict__ desc) {
     const uint32_t i = begin + blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= end) return;
-    rows[i].off_a += base;
-    rows[i].off_b += base;
-    pair_ids[i] = rows[i].pair_id;
+    gpudiff_pair_row r = rows[i];
+    r.off_a += base;
+    r.off_b += base;
+    rows[i].off_a = r.off_a;
+    rows[i].off_b = r.off_b;
+    pair_ids[i] = r.pair_id;
+    if (desc) {
+        const gpudiff_pair_desc d = gpudiff_pair_desc_pack(&r);
+        desc[i] = make_uint4(d.w[0], d.w[1], d.w[2], d.w[3]);
+    }
 }
 
 // ---------------------------------------------------------------- launchers
@@ -1256,9 +1318,9 @@ static inline uint32_t grid_for(uint64_t waves_wanted, uint32_t cap_blocks) {
 static constexpr uint32_t kPersistBlocks = 256 * 8;
 
 hipError_t launch_rebase(hipStream_t s, gpudiff_pair_row* rows, uint32_t begin, uint32_t end, uint64_t base,
-                         uint32_t* pair_ids) {
+                         uint32_t* pair_ids, uint4* desc) {
     if (end <= begin) return hipSuccess;
-    k_rebase_rows<<<(end - begin + 255) / 256, 256, 0, s>>>(rows, begin, end, base, pair_ids);
+    k_rebase_rows<<<(end - begin + 255) / 256, 256, 0, s>>>(rows, begin, end, base, pair_ids, desc);
     return hipGetLastError();
 }
 
@@ -1280,20 +1342,24 @@ hipError_t launch_move_blobs(hipStream_t s, const uint8_t* src, uint8_t* dst, co
 // 2 / 4 / 12 chunks in flight, plain loads, rows prefetched into LDS, static striding.
 typedef void (*K2Fn)(const gpudiff_pair_row*, const uint8_t*, uint32_t, uint8_t*, uint32_t*, uint4*, uint32_t, uint32_t,
                      uint64_t*, uint8_t*, uint32_t, uint32_t, uint32_t, uint32_t*, uint32_t*, uint8_t*, uint64_t,
-                     uint32_t*, uint32_t, const uint32_t*);
-constexpr uint32_t kK2Kernels = 4;
+                     uint32_t*, uint32_t, const uint32_t*, const uint4*);
+// ... and the default kernel and its timeline build once more, reading 16-B pair descriptors in place of the rows
+// (DiffBuffers::desc; the deep-pair kernels keep the rows: 0.1% of their bytes, and they sit at 200 VGPRs)
+constexpr uint32_t kK2Kernels = 8;
 static K2Fn k2_kernel(uint32_t k) {
     switch (k) {
-        case 1: return k_compare_flat<16, 1, false, true>;
+        case 1: case 5: return k_compare_flat<16, 1, false, true>;
         case 2: return k_compare_flat<8, 1, true>;
-        case 3: return k_compare_flat<16, 1, true, true>;
+        case 3: case 7: return k_compare_flat<16, 1, true, true>;
+        case 4: return k_compare_flat<8, 1, false, false, true>;
+        case 6: return k_compare_flat<8, 1, true, false, true>;
         default: return k_compare_flat<8, 1>;
     }
 }
 
 constexpr uint64_t kK2BigPairBytes = 16384;
 static uint32_t k2_variant_of(const DiffBuffers& b) {
-    return (b.avg_pair_bytes >= kK2BigPairBytes ? 1u : 0u) | (b.k2_timeline ? 2u : 0u);
+    return (b.avg_pair_bytes >= kK2BigPairBytes ? 1u : 0u) | (b.k2_timeline ? 2u : 0u) | (b.desc ? 4u : 0u);
 }
 
 constexpr uint32_t kK2LptMax = 16384;  // largest-first rounds: at most this many pairs (one block sorts them in LDS)
@@ -1472,7 +1538,7 @@ hipError_t launch_compare(hipStream_t s, const DiffBuffers& b) {
     const uint32_t sub_arg = sub | (tq << 8) | (lpt ? kK2LptRounds << 20 | 1u << 22 : 0u);
     k2_kernel(v)<<<grid, 256, 0, s>>>(b.rows, b.pool, b.n_pairs, b.flags, b.caps, cc, 0u, nch, b.arena_h, b.arena_k, 0u,
                                       b.arena_per_wave, b.arena_per_wave, b.path_src, b.path_cnt, b.nbits, b.hash_mask,
-                                      b.summary, sub_arg, perm);
+                                      b.summary, sub_arg, perm, (v & 1u) ? nullptr : b.desc);
     return hipGetLastError();
 }
 

@@ -381,7 +381,7 @@ int gpudiff_store_submit(gpudiff_ctx* c, gpudiff_store* s, const gpudiff_event* 
     if (n) HIPCHK(hipMemcpyAsync(d->rows, hr, n * sizeof(gpudiff_pair_row), hipMemcpyHostToDevice, c->stream));
     if (hb->used) HIPCHK(hipEventRecord(hb->used, c->stream));
     if (n) {
-        HIPCHK(launch_rebase(c->stream, d->rows, 0, (uint32_t)n, 0, d->pair_ids));  // pair_ids SoA copy
+        HIPCHK(launch_rebase(c->stream, d->rows, 0, (uint32_t)n, 0, d->pair_ids, nullptr));  // pair_ids SoA copy
     }
     s->used += total;
     d->pool = space;

@@ -35,6 +35,7 @@ OPT_PATH_STRINGS = 0x8000000  # device-encoded batches: K15/K16 render the chang
 # device-encoded batches: K21/K22 render every changed leaf's old and new value as JSON text
 # (DiffResult.path_values)
 OPT_PATH_VALUES = 0x80000000
+OPT_K2_ROWS = 0x40  # diagnostic: K2 reads the 64-B rows, not the 16-B pair descriptors (same results)
 OPT_ARENA_SHIFT = 21  # test hook: 4 bits, the K2 wave arenas shrunk 2^k-fold (forces the deferred K4 path)
 OPT_SMALL_PASS = 0x20000000  # a pass of 1..SMALL_PASS_MAX_PAIRS pairs runs as one kernel (K20) with one read-back
 SMALL_PASS_MAX_PAIRS = 4096  # GPUDIFF_SMALL_PASS_MAX_PAIRS
