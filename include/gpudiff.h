@@ -296,7 +296,10 @@ int gpudiff_encode_pairs(gpudiff_ctx* ctx, const gpudiff_json_pair* pairs, size_
 int gpudiff_hbatch_info_get(const gpudiff_hbatch* hb, gpudiff_hbatch_info* info);
 /* empty host batch (pinned on a GPU context) for pairs encoded elsewhere in the
  * canonical format (pre-encoded replays, synthetic populations); the caller
- * fills *pool and *rows (row offsets relative to *pool) before appending */
+ * fills *pool and *rows (row offsets relative to *pool) before appending.
+ * The decision kernel trusts a row's structural fields as it always trusted the sizes: a row whose flags_b carries
+ * GPUDIFF_OBJ_SPEC_KEYS_EQ (gpudiff_format.h) states that both sides' spec keys[] are equal, and the whole 128-byte
+ * lines holding only those keys are then not read or compared.  A caller that cannot vouch for it leaves the bit 0. */
 int gpudiff_hbatch_create(gpudiff_ctx* ctx, uint64_t pool_bytes, size_t n_pairs, uint64_t total_leaves,
                           gpudiff_hbatch** out, uint8_t** pool, gpudiff_pair_row** rows);
 /* reuses a host batch (staging ring): waits for its last H2D copy, grows the
@@ -367,6 +370,10 @@ void gpudiff_dbatch_free(gpudiff_ctx* ctx, gpudiff_dbatch* db);
  * 4/3 of the optimum (Graham's bound) and within one cluster's weight of the mean. */
 int gpudiff_cluster_bytes(const gpudiff_pair_row* rows, size_t n, uint32_t n_clusters, uint64_t* out);
 int gpudiff_shard_lpt(const uint64_t* weights, uint32_t n_clusters, uint32_t world, int32_t* owner);
+/* *out = the sum of gpudiff_pair_stream_bytes (gpudiff_format.h) over the rows: what the decision kernel reads for them
+ * from their descriptors -- the format's bytes less the 64-B rows and the key holes.  For measurements: the shard
+ * weight stays gpudiff_cluster_bytes. */
+int gpudiff_rows_stream_bytes(const gpudiff_pair_row* rows, size_t n, uint64_t* out);
 
 /* ---- diff (the hot path) ---- */
 /* enqueue K2..K6 on the context stream; returns immediately */

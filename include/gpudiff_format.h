@@ -71,6 +71,13 @@
 #define GPUDIFF_OBJ_HAS_STATUS 0x1u   /* top-level "status" key present (even null) */
 #define GPUDIFF_OBJ_DECODE_ERR 0x2u   /* JSON failed the Go decode rules */
 #define GPUDIFF_OBJ_FRESH 0x4u        /* object store: blob uploaded with this batch (informational) */
+/* flags_b only: spec_l_a == spec_l_b and A's and B's spec keys[] are element for element equal -- with the
+ * injectivity the encoder has just verified, the same paths.  A structural fact like the sizes, stated by the
+ * producer that sorted both key lists (PairEncoder::encode_flat), never on a decode-error row; K2 trusts it
+ * exactly as it trusts the sizes and leaves the whole lines that hold only spec keys out of its stream
+ * (gpudiff_keys_hole).  Additive: a producer that leaves it 0 (the object stores, an older encoder) gets the keys
+ * streamed as before. */
+#define GPUDIFF_OBJ_SPEC_KEYS_EQ 0x8u
 /* object store: the path table kept after a resident blob's segments (the
  * "trailer"), which makes the store's old-vs-new path check exact.  Its n
  * entries are the region leaves and all their ancestors except the root,
@@ -131,6 +138,26 @@ GPUDIFF_HD static inline uint64_t gpudiff_blob_body(uint32_t sl, uint32_t sar, u
            ~(uint64_t)(GPUDIFF_BLOB_ALIGN - 1u);
 }
 
+/* ---- key holes: the part of a segment's keys[L] that K2 may skip when the row says the two sides' keys are equal
+ * (GPUDIFF_OBJ_SPEC_KEYS_EQ).  keys[] occupies bytes [8 L, 12 L) of the segment; the hole is the whole
+ * GPUDIFF_KEYS_HOLE_UNIT-byte units inside it, so with the segment at the blob's (line-aligned) start it is whole
+ * lines of memory.  The partial units at both ends -- the last values, the first metas and a few keys -- are still
+ * streamed.  *hs: the hole's first 16-B chunk, *hl: its chunks (0: no hole).  L = 32 is the first with a hole
+ * (one line), L = 33..42 have none, L = 184 skips 640 B a side. */
+#ifndef GPUDIFF_KEYS_HOLE_UNIT
+#define GPUDIFF_KEYS_HOLE_UNIT 128u
+#endif
+GPUDIFF_HD static inline void gpudiff_keys_hole(uint32_t l, uint32_t* hs, uint32_t* hl) {
+    const uint64_t u = GPUDIFF_KEYS_HOLE_UNIT;
+    const uint64_t lo = (8ull * l + (u - 1u)) / u * u, hi = 12ull * l / u * u;
+    *hs = hi > lo ? (uint32_t)(lo >> 4) : 0u;
+    *hl = hi > lo ? (uint32_t)((hi - lo) >> 4) : 0u;
+}
+/* streamed spec chunk k of a pair with the hole (hs, hl) is chunk k + (k >= hs ? hl : 0) of the segment */
+GPUDIFF_HD static inline uint32_t gpudiff_hole_chunk(uint32_t k, uint32_t hs, uint32_t hl) {
+    return k + (k >= hs ? hl : 0u);
+}
+
 /* B_pair: the bytes the decision kernel (K2) reads for one pair -- the 64-B row, the flag byte and, per
  * object, the compared 16-B chunks: the whole body (segments + zero pad) when both regions' sizes match
  * and B has status; the spec segment when only the spec sizes match (padded to the line too when neither
@@ -159,7 +186,8 @@ GPUDIFF_HD static inline uint64_t gpudiff_pair_compare_bytes(const gpudiff_pair_
  *
  *   word 0, 1   off_a >> 7, off_b >> 7                  (blobs are GPUDIFF_BLOB_ALIGN aligned)
  *   bits  0-18  spec segment bytes of A, in 16-B units  (word 2 | word 3 << 32)
- *   bits 19-37  spec segment bytes of B, in 16-B units
+ *   bits 19-37  spec segment bytes of B, in 16-B units; under SPEC_EQ (B's equal A's) the skip L instead: the spec
+ *               leaf count when the row carries GPUDIFF_OBJ_SPEC_KEYS_EQ, no error and a non-empty key hole, else 0
  *   bits 38-56  status segment bytes of A, in 16-B units
  *   bits 57-63  GPUDIFF_PD_* >> 0
  *
@@ -184,18 +212,21 @@ typedef struct gpudiff_pair_desc {
     uint32_t w[4];
 } gpudiff_pair_desc;
 
-/* what K2's stream needs of a pair: n1 spec chunks from off, n2 status chunks from off + 16 n1 + adj (per side),
- * and the GPUDIFF_PD_* bits its decisions read */
+/* what K2's stream needs of a pair: n1 streamed spec chunks -- chunk k at off + 16 gpudiff_hole_chunk(k, hs, hl) --
+ * n2 status chunks from off + 16 n1 + adj (per side), and the GPUDIFF_PD_* bits its decisions read */
 typedef struct gpudiff_pair_geom {
     uint64_t off_a, off_b;
     uint32_t n1, n2, adj_a, adj_b;
     uint32_t bits;
+    uint32_t hs, hl; /* the key hole left out of the n1 spec chunks (16-B chunks; hl 0: none) */
 } gpudiff_pair_geom;
 
 /* the stream's chunk counts from the segment bytes and the bits: K2's rule (gpudiff_pair_compare_bytes counts the
- * same chunks) */
+ * same chunks, the hole included).  skip_l: the spec leaf count of a pair whose spec keys need no compare, else 0;
+ * a count whose keys would not lie inside the streamed spec span (never a packer's) is taken as 0 */
 GPUDIFF_HD static inline gpudiff_pair_geom gpudiff_pair_geom_of(uint64_t off_a, uint64_t off_b, uint32_t seg_a,
-                                                                uint32_t seg_b, uint32_t seg_t, uint32_t bits) {
+                                                                uint32_t seg_b, uint32_t seg_t, uint32_t bits,
+                                                                uint32_t skip_l) {
     gpudiff_pair_geom g;
     const int ok = !(bits & GPUDIFF_PD_ERR);
     const int spec_sz = (bits & GPUDIFF_PD_SPEC_EQ) != 0u;
@@ -205,6 +236,11 @@ GPUDIFF_HD static inline gpudiff_pair_geom gpudiff_pair_geom_of(uint64_t off_a, 
     g.off_b = off_b;
     g.n1 = (ok && spec_sz) ? ((!stat_sz && (bits & GPUDIFF_PD_NO_STAT)) ? ((seg_a + 127u) & ~127u) : seg_a) >> 4 : 0u;
     g.n2 = (ok && stat_sz) ? (spec_sz ? r128 - seg_a : seg_t) >> 4 : 0u;
+    g.hs = g.hl = 0u;
+    if (skip_l && (uint64_t)skip_l * 12u <= 16ull * g.n1) {
+        gpudiff_keys_hole(skip_l, &g.hs, &g.hl);
+        g.n1 -= g.hl;
+    }
     g.adj_a = seg_a - 16u * g.n1;
     g.adj_b = seg_b - 16u * g.n1;
     g.bits = bits;
@@ -221,11 +257,11 @@ GPUDIFF_HD static inline uint32_t gpudiff_pair_row_bits(const gpudiff_pair_row* 
            ((r->stat_l_a | r->stat_l_b | r->stat_ar_a | r->stat_ar_b) == 0u ? GPUDIFF_PD_NO_STAT : 0u);
 }
 
-/* the same from the row itself (an escape's lane in K2) */
+/* the same from the row itself (an escape's lane in K2, the row-path kernels): never a hole */
 GPUDIFF_HD static inline gpudiff_pair_geom gpudiff_pair_row_geom(const gpudiff_pair_row* r) {
     return gpudiff_pair_geom_of(r->off_a, r->off_b, (uint32_t)gpudiff_seg_bytes(r->spec_l_a, r->spec_ar_a),
                                 (uint32_t)gpudiff_seg_bytes(r->spec_l_b, r->spec_ar_b),
-                                (uint32_t)gpudiff_seg_bytes(r->stat_l_a, r->stat_ar_a), gpudiff_pair_row_bits(r));
+                                (uint32_t)gpudiff_seg_bytes(r->stat_l_a, r->stat_ar_a), gpudiff_pair_row_bits(r), 0u);
 }
 
 GPUDIFF_HD static inline gpudiff_pair_desc gpudiff_pair_desc_pack(const gpudiff_pair_row* r) {
@@ -244,7 +280,14 @@ GPUDIFF_HD static inline gpudiff_pair_desc gpudiff_pair_desc_pack(const gpudiff_
         return d;
     }
     {
-        const uint64_t zw = (sa >> 4) | ((sb >> 4) << GPUDIFF_PD_SIZE_BITS) | ((st >> 4) << (2u * GPUDIFF_PD_SIZE_BITS)) |
+        /* under SPEC_EQ sb == sa: the field carries the skip L (16 L <= sa, so it fits) */
+        uint64_t f1 = sb >> 4;
+        if (bits & GPUDIFF_PD_SPEC_EQ) {
+            uint32_t hs = 0, hl = 0;
+            if ((r->flags_b & GPUDIFF_OBJ_SPEC_KEYS_EQ) && !(bits & GPUDIFF_PD_ERR)) gpudiff_keys_hole(r->spec_l_a, &hs, &hl);
+            f1 = hl ? r->spec_l_a : 0u;
+        }
+        const uint64_t zw = (sa >> 4) | (f1 << GPUDIFF_PD_SIZE_BITS) | ((st >> 4) << (2u * GPUDIFF_PD_SIZE_BITS)) |
                             ((uint64_t)bits << (3u * GPUDIFF_PD_SIZE_BITS));
         d.w[0] = (uint32_t)(r->off_a >> 7);
         d.w[1] = (uint32_t)(r->off_b >> 7);
@@ -259,10 +302,22 @@ GPUDIFF_HD static inline int gpudiff_pair_desc_is_escape(uint32_t w3) { return w
 /* of a descriptor that is not the escape */
 GPUDIFF_HD static inline gpudiff_pair_geom gpudiff_pair_desc_unpack(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3) {
     const uint64_t zw = ((uint64_t)w3 << 32) | w2;
-    return gpudiff_pair_geom_of((uint64_t)w0 << 7, (uint64_t)w1 << 7, (w2 & GPUDIFF_PD_SIZE_MAX) << 4,
-                                ((uint32_t)(zw >> GPUDIFF_PD_SIZE_BITS) & GPUDIFF_PD_SIZE_MAX) << 4,
-                                ((w3 >> (2u * GPUDIFF_PD_SIZE_BITS - 32u)) & GPUDIFF_PD_SIZE_MAX) << 4,
-                                w3 >> (3u * GPUDIFF_PD_SIZE_BITS - 32u));
+    const uint32_t bits = w3 >> (3u * GPUDIFF_PD_SIZE_BITS - 32u);
+    const uint32_t seg_a = (w2 & GPUDIFF_PD_SIZE_MAX) << 4;
+    const uint32_t f1 = (uint32_t)(zw >> GPUDIFF_PD_SIZE_BITS) & GPUDIFF_PD_SIZE_MAX;
+    const int eq = (bits & GPUDIFF_PD_SPEC_EQ) != 0u;
+    return gpudiff_pair_geom_of((uint64_t)w0 << 7, (uint64_t)w1 << 7, seg_a, eq ? seg_a : f1 << 4,
+                                ((w3 >> (2u * GPUDIFF_PD_SIZE_BITS - 32u)) & GPUDIFF_PD_SIZE_MAX) << 4, bits,
+                                eq ? f1 : 0u);
+}
+
+/* the bytes the descriptor kernel reads for one pair: its 16-B descriptor and both sides' streamed chunks, key holes
+ * left out (an escape's pair streams from its row: no hole).  gpudiff_pair_compare_bytes stays the format's bytes. */
+GPUDIFF_HD static inline uint64_t gpudiff_pair_stream_bytes(const gpudiff_pair_row* r) {
+    const gpudiff_pair_desc d = gpudiff_pair_desc_pack(r);
+    const gpudiff_pair_geom g = gpudiff_pair_desc_is_escape(d.w[3]) ? gpudiff_pair_row_geom(r)
+                                                                   : gpudiff_pair_desc_unpack(d.w[0], d.w[1], d.w[2], d.w[3]);
+    return sizeof(gpudiff_pair_desc) + 32ull * ((uint64_t)g.n1 + g.n2);
 }
 
 GPUDIFF_HD static inline uint32_t gpudiff_meta(uint32_t tag, uint32_t len) { return (len << 3) | tag; }

@@ -609,6 +609,14 @@ int gpudiff_cluster_bytes(const gpudiff_pair_row* rows, size_t n, uint32_t n_clu
     return GPUDIFF_OK;
 }
 
+int gpudiff_rows_stream_bytes(const gpudiff_pair_row* rows, size_t n, uint64_t* out) {
+    if ((n && !rows) || !out) return GPUDIFF_E_INVAL;
+    uint64_t sum = 0;
+    for (size_t i = 0; i < n; i++) sum += gpudiff_pair_stream_bytes(&rows[i]);
+    *out = sum;
+    return GPUDIFF_OK;
+}
+
 int gpudiff_shard_lpt(const uint64_t* weights, uint32_t n_clusters, uint32_t world, int32_t* owner) {
     if (world == 0 || world > 0x7FFFFFFFu || (n_clusters && (!weights || !owner))) return GPUDIFF_E_INVAL;
     try {

@@ -290,6 +290,11 @@ void PairEncoder::encode_flat(FlatObject* fa, FlatObject* fb, uint32_t pair_id, 
     write_blob(*fb, pool, &row.off_b, &row.spec_l_b, &row.spec_ar_b, &row.stat_l_b, &row.stat_ar_b);
     row.flags_a = fa->flags | (seed << GPUDIFF_OBJ_SEED_SHIFT);
     row.flags_b = fb->flags | (seed << GPUDIFF_OBJ_SEED_SHIFT);
+    // assign_seed left both sides' leaves sorted by hash: the keys[] arrays just written are the two h sequences,
+    // so one pass tells whether they are element for element equal (the same paths: the union is injective)
+    bool keys_eq = fa->spec.size() == fb->spec.size();
+    for (size_t i = 0; keys_eq && i < fa->spec.size(); i++) keys_eq = (uint32_t)fa->spec[i].h == (uint32_t)fb->spec[i].h;
+    if (keys_eq) row.flags_b |= GPUDIFF_OBJ_SPEC_KEYS_EQ;
 }
 
 void PairEncoder::encode_nodes(const Node* a, const Node* b, uint32_t pair_id, uint32_t cluster_id,

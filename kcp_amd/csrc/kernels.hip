@@ -150,7 +150,8 @@ __global__ __launch_bounds__(256) void k_scan_apply(const V* in, const uint32_t*
 struct StreamLog {
     uint32_t cnt[2][64];             // [status][pair]
     uint32_t ent[2][64][kSpLogCap];  // sp_entry(the chunk's index in the item's stream, its differing dwords)
-    uint32_t first[64], n1[64];      // a pair's first chunk in the item's stream, its spec chunks
+    uint32_t first[64], n1[64];      // a pair's first chunk in the item's stream, its streamed spec chunks
+    uint32_t hole[64];               // its key hole (sp_hole_word): a logged spec chunk's place in the segment
 };
 
 // The changed paths of a size-matched region from its c <= kSpLogCap logged chunks, by stream_paths.h's rule (a
@@ -158,10 +159,12 @@ struct StreamLog {
 // its order (ascending leaf = ascending key), with its *weq_all.  Returns the path count, or kSpRefuse with
 // nothing written that the join does not overwrite: the caller then joins the region.
 __device__ uint32_t stream_region(const RegionView& A, const RegionView& B, uint64_t seg, const uint32_t* ent,
-                                  uint32_t c, uint32_t g0, uint8_t region_bit, uint64_t* __restrict__ out_h,
-                                  uint8_t* __restrict__ out_k, uint32_t out_base, uint32_t lane, bool* weq_all) {
+                                  uint32_t c, uint32_t g0, uint32_t hole, uint8_t region_bit,
+                                  uint64_t* __restrict__ out_h, uint8_t* __restrict__ out_k, uint32_t out_base,
+                                  uint32_t lane, bool* weq_all) {
     const uint32_t nc = 4u * c;  // <= 16 candidate lanes: dword (lane & 3) of entry (lane >> 2)
-    const uint32_t e = lane < nc ? ent[lane >> 2] - sp_entry(g0, 0u) : 0u;  // g0: the region's first chunk
+    // g0: the region's first chunk; hole: the streamed index back to the chunk's place in the segment
+    const uint32_t e = lane < nc ? sp_entry_unhole(ent[lane >> 2] - sp_entry(g0, 0u), hole) : 0u;
     const bool cand = lane < nc && ((sp_entry_dwords(e) >> (lane & 3u)) & 1u);
     const uint64_t b = sp_entry_byte(e, lane & 3u);
     const SpWhere w = sp_classify(b, A.L);
@@ -237,8 +240,8 @@ __device__ uint32_t stream_pair(const gpudiff_pair_row& r, uint32_t f, const uin
         const uint32_t g0 = uni(log->first[k]);
         uint32_t got = kSpRefuse;
         if (c >= 1u && c <= kSpLogCap)
-            got = stream_region(A, B, seg_bytes(r.spec_l_a, r.spec_ar_a), log->ent[0][k], c, g0, 0, out_h, out_k, base + n,
-                                lane, &spec_weq);
+            got = stream_region(A, B, seg_bytes(r.spec_l_a, r.spec_ar_a), log->ent[0][k], c, g0, uni(log->hole[k]), 0,
+                                out_h, out_k, base + n, lane, &spec_weq);
         if (got == kSpRefuse) got = join_region<true>(A, B, 0, out_h, out_k, base + n, lane, &spec_weq);
         else (*n_stream)++;
         n += got;
@@ -250,7 +253,7 @@ __device__ uint32_t stream_pair(const gpudiff_pair_row& r, uint32_t f, const uin
         const uint32_t g0 = uni(log->first[k]) + uni(log->n1[k]);
         uint32_t got = kSpRefuse;
         if (c >= 1u && c <= kSpLogCap)
-            got = stream_region(A, B, seg_bytes(r.stat_l_a, r.stat_ar_a), log->ent[1][k], c, g0,
+            got = stream_region(A, B, seg_bytes(r.stat_l_a, r.stat_ar_a), log->ent[1][k], c, g0, 0u,
                                 GPUDIFF_PATH_REGION_STATUS, out_h, out_k, base + n, lane, &stat_weq);
         if (got == kSpRefuse)
             got = join_region<true>(A, B, GPUDIFF_PATH_REGION_STATUS, out_h, out_k, base + n, lane, &stat_weq);
@@ -749,10 +752,12 @@ __global__ __launch_bounds__(256, MINB) void k_compare_flat(const gpudiff_pair_r
         slog = &stream_logs[uni(threadIdx.x >> 6)];
     }
     // one pass of a wave over chunks [base, base + 64 U) of an item's flattened stream (lane k's registers: pair k's
-    // inclusive chunk prefix, first chunk, spec chunks, arena adjustments and blob offsets); mismatching chunks mark
-    // their pairs in mis_s / mis_t
+    // inclusive chunk prefix, first chunk, spec chunks, arena adjustments and blob offsets; DESC: its key hole as
+    // sp_hole_word, which the spec chunks from the hole's start on step over); mismatching chunks mark their pairs in
+    // mis_s / mis_t
     auto stream_pass = [&](uint32_t base, uint32_t total, uint32_t incl, uint32_t first, uint32_t n1, uint32_t adj_a,
-                           uint32_t adj_b, uint64_t off_a, uint64_t off_b, uint64_t& mis_s, uint64_t& mis_t) {
+                           uint32_t adj_b, uint64_t off_a, uint64_t off_b, uint64_t& mis_s, uint64_t& mis_t,
+                           [[maybe_unused]] uint32_t hole = 0u) {
         u32x4 va[U], vb[U];
         uint32_t own[U];
         bool st[U], act[U];
@@ -766,13 +771,19 @@ __global__ __launch_bounds__(256, MINB) void k_compare_flat(const gpudiff_pair_r
                 if (shfl32(incl, o + s - 1u) <= g) o += s;
             const uint32_t k = g - shfl32(first, o);
             st[u] = k >= shfl32(n1, o);
-            const uint32_t xa = shfl32(adj_a, o), xb = shfl32(adj_b, o);
+            // (DESC: one adjustment serves both sides, B's own is folded into off_b where the descriptor is unpacked)
+            const uint32_t xa = shfl32(adj_a, o), xb = DESC ? xa : shfl32(adj_b, o);
             const uint64_t oa = shfl64(off_a, o), ob = shfl64(off_b, o);
             own[u] = HELP ? o : o | (st[u] ? 64u : 0u);  // (the default kernel: the log's slot index)
             const uint64_t rel = 16ull * k;
+            uint32_t ha = 0;  // the hole's bytes, for a spec chunk past its start (both sides: the sizes are equal)
+            if constexpr (DESC) {
+                const uint32_t hw = shfl32(hole, o);
+                ha = k >= sp_hole_start(hw) ? sp_hole_bytes(hw) : 0u;
+            }
             if (act[u]) {
-                va[u] = __builtin_nontemporal_load((const u32x4*)(pool + oa + rel + (st[u] ? xa : 0u)));
-                vb[u] = __builtin_nontemporal_load((const u32x4*)(pool + ob + rel + (st[u] ? xb : 0u)));
+                va[u] = __builtin_nontemporal_load((const u32x4*)(pool + oa + rel + (st[u] ? xa : ha)));
+                vb[u] = __builtin_nontemporal_load((const u32x4*)(pool + ob + rel + (st[u] ? xb : ha)));
             }
         }
         if constexpr (HELP) {
@@ -911,6 +922,7 @@ __global__ __launch_bounds__(256, MINB) void k_compare_flat(const gpudiff_pair_r
         uint64_t off_a, off_b;
         bool err, spec_sz, has_st_b, stat_sz;
         uint32_t n1, n2, adj_a, adj_b;
+        [[maybe_unused]] uint32_t hole = 0;  // DESC: the pair's key hole (sp_hole_word)
         // DESC: the pair's GPUDIFF_PD_* bits | kPdRow (its descriptor is the escape): all the stream leaves alive
         [[maybe_unused]] uint32_t dbits = 0;
         constexpr uint32_t kPdRow = 0x80u;
@@ -930,7 +942,13 @@ __global__ __launch_bounds__(256, MINB) void k_compare_flat(const gpudiff_pair_r
             has_st_b = (dbits & GPUDIFF_PD_HAS_ST_B) != 0u;
             stat_sz = has_st_b && (dbits & GPUDIFF_PD_STAT_EQ) != 0u;
             n1 = valid ? g.n1 : 0u, n2 = valid ? g.n2 : 0u;
-            adj_a = g.adj_a, adj_b = g.adj_b;
+            // B's status chunk k lies at off_b + 16 k + adj_b.  A pair has spec chunks only with equal spec sizes, and then
+            // adj_b == adj_a; without them every chunk takes the adjustment.  So adj_b - adj_a (= seg_b - seg_a) goes
+            // into off_b once and the stream adds adj_a on both sides: the lane register and the cross-lane read per
+            // chunk this frees carry the key hole instead
+            off_b += (uint64_t)g.adj_b - (uint64_t)g.adj_a;  // (each zero-extended, as the stream adds adj_a)
+            adj_a = adj_b = g.adj_a;
+            hole = sp_hole_word(g.hs, g.hl);
         } else {
             off_a = ((uint64_t)v0.y << 32) | v0.x, off_b = ((uint64_t)v0.w << 32) | v0.z;
             err = valid && ((v3.x | v3.y) & GPUDIFF_OBJ_DECODE_ERR) != 0u;
@@ -994,9 +1012,10 @@ __global__ __launch_bounds__(256, MINB) void k_compare_flat(const gpudiff_pair_r
             slog->cnt[1][lane] = 0u;
             slog->first[lane] = first;
             slog->n1[lane] = n1;
+            slog->hole[lane] = hole;
             uint32_t pass = 0;
             for (uint32_t base = 0; base < total; base += 64u * U, pass++) {
-                stream_pass(base, total, incl, first, n1, adj_a, adj_b, off_a, off_b, mis_s, mis_t);
+                stream_pass(base, total, incl, first, n1, adj_a, adj_b, off_a, off_b, mis_s, mis_t, hole);
                 if (pass == 0 && it < n_main && lane == 0) tk = atomicAdd(ctr, 1u);  // back by the next pass
             }
             if (pass == 0 && it < n_main && lane == 0) tk = atomicAdd(ctr, 1u);  // an item with nothing to stream

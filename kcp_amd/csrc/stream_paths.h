@@ -37,6 +37,20 @@ GD_SP_HD inline uint32_t sp_entry(uint32_t chunk, uint32_t dwords) { return (chu
 GD_SP_HD inline uint32_t sp_entry_dwords(uint32_t e) { return e & 15u; }
 GD_SP_HD inline uint64_t sp_entry_byte(uint32_t e, uint32_t d) { return 16ull * (e >> 4) + 4u * d; }
 
+// A pair's key hole (gpudiff_keys_hole: hs, hl in 16-B chunks, both multiples of 8 -- whole lines) as the one word K2
+// keeps per lane and per pair of the log: hs / 8 | hl / 8 << 16; 0: no hole.  Streamed spec chunk k of the pair is
+// chunk k + (k >= hs ? hl : 0) of the segment (gpudiff_hole_chunk): the stream adds sp_hole_bytes to the address, and a
+// logged entry goes back through sp_entry_unhole before sp_entry_byte, so the rule above sees segment bytes.
+static_assert(GPUDIFF_KEYS_HOLE_UNIT % 128u == 0u, "sp_hole_word keeps the hole in 128-B lines");
+GD_SP_HD inline uint32_t sp_hole_word(uint32_t hs, uint32_t hl) { return (hs >> 3) | ((hl >> 3) << 16); }
+GD_SP_HD inline uint32_t sp_hole_start(uint32_t w) { return (w & 0xFFFFu) << 3; }   // chunks; only read when hl != 0
+GD_SP_HD inline uint32_t sp_hole_chunks(uint32_t w) { return (w >> 16) << 3; }
+GD_SP_HD inline uint32_t sp_hole_bytes(uint32_t w) { return (w >> 16) << 7; }
+// the entry of streamed chunk k as the entry of the segment's chunk
+GD_SP_HD inline uint32_t sp_entry_unhole(uint32_t e, uint32_t w) {
+    return e + ((e >> 4) >= sp_hole_start(w) ? sp_entry(sp_hole_chunks(w), 0u) : 0u);
+}
+
 // arena bytes of a leaf's value: a long string's tail past its first 8 bytes, zero padded to 4; must equal
 // gpudiff_meta_arena (include/gpudiff_format.h), restated here because K2 compiles it
 GD_SP_HD inline uint32_t sp_meta_arena(uint32_t m) {
