@@ -406,6 +406,62 @@ int gpudiff_pass_stats_get(gpudiff_ctx* ctx, gpudiff_pass_stats* out);
 int gpudiff_submit(gpudiff_ctx* ctx, const gpudiff_json_pair* pairs, size_t n,
                    gpudiff_ticket* ticket);
 
+/* ---- per-cluster index of a pass's dirty IDs ----
+ * The reference runs one syncer per logical cluster (pkg/reconciler/cluster/cluster.go:125-138), each with its own
+ * work queue fed by AddToQueue (pkg/syncer/syncer.go:222-224).  The index says whose queue a dirty pair belongs to:
+ * a pure function of the waited pass's rows i = 0..n-1 in batch order (pair_id[i], cluster_id[i], final flags[i]):
+ *   cluster_ids  the distinct cluster ids with at least one pair carrying GPUDIFF_SPEC_DIRTY or GPUDIFF_STATUS_DIRTY,
+ *                ascending as unsigned 32-bit values (any u32 is a legal id, 0 and 0xFFFFFFFF included);
+ *   spec_ids     the pair_id of every spec-dirty pair, ordered by (cluster_id ascending, batch position ascending);
+ *   status_ids   the same for the status-dirty pairs;
+ *   spec_off / status_off  cluster_ids[j] owns spec_ids[spec_off[j], spec_off[j + 1]) and the like slice of
+ *                status_ids (a listed cluster may have an empty slice of one kind).
+ * A decode-error pair is dirty in both kinds, as its flags say; the no-op bits play no part.  When the batch's dirty
+ * pairs already lie in non-decreasing cluster order (a resident batch laid out by cluster), spec_ids and status_ids
+ * equal the result's spec_dirty_ids and status_dirty_ids element for element and no sort runs.
+ *
+ * gpudiff_cluster_index_get builds it on the device (kernels K23 - K25, a radix sort between them only when the dirty
+ * list does not ascend by cluster) from what the pass left in HBM, for tickets of gpudiff_diff (on a batch or on a
+ * view, which reads its base's rows) and of gpudiff_submit batches the host encoded.  Valid after gpudiff_wait on the
+ * ticket has returned and until that batch is diffed or submitted again.  On demand: a caller that never makes the
+ * call launches and allocates nothing.  At most three host synchronisations per call, none when nothing is dirty.
+ * GPUDIFF_E_STATE: an unknown, unwaited or superseded ticket, and a ticket whose flags the host may still patch
+ * (device-encoded gpudiff_submit batches, every gpudiff_store_submit ticket: their deferred rows' final flags live on
+ * the host); GPUDIFF_E_NODEVICE: a host-only context; GPUDIFF_E_CAPACITY: out of device memory; GPUDIFF_E_DEVICE
+ * also when the index's counts disagree with the pass's own (never a silently wrong index).
+ * The arrays belong to the index until gpudiff_cluster_index_release (ctx may be NULL for a host-built index). */
+typedef struct gpudiff_cluster_index {
+    size_t n_clusters;
+    const uint32_t* cluster_ids;   /* [n_clusters] ascending, distinct */
+    const uint32_t* spec_off;      /* [n_clusters + 1] */
+    const uint32_t* status_off;    /* [n_clusters + 1] */
+    size_t n_spec, n_status;       /* == the result's n_spec_dirty / n_status_dirty */
+    const uint32_t* spec_ids;
+    const uint32_t* status_ids;
+    uint32_t sorted_on_device;     /* 0: the dirty list was already in cluster order, no sort ran */
+    void* internal;
+} gpudiff_cluster_index;
+int gpudiff_cluster_index_get(gpudiff_ctx* ctx, gpudiff_ticket ticket, gpudiff_cluster_index* out);
+void gpudiff_cluster_index_release(gpudiff_ctx* ctx, gpudiff_cluster_index* idx);
+/* The same function on the host, one thread, no GPU needed (host-only callers, the tests' second implementation, the
+ * measurements' baseline): flags / pair_ids / cluster_ids of n rows in batch order.  sorted_on_device is 0.
+ * GPUDIFF_E_INVAL: n > 0xFFFFFFFF or a missing array. */
+int gpudiff_cluster_index_host(const uint8_t* flags, const uint32_t* pair_ids, const uint32_t* cluster_ids, size_t n,
+                               gpudiff_cluster_index* out);
+/* what the context's gpudiff_cluster_index_get calls cost since gpudiff_open; kernel_ms needs GPUDIFF_OPT_TIMING (HIP
+ * events around K23, around the sort + K24 + scan, and around K25, summed over timed_calls).  GPUDIFF_E_NODEVICE on a
+ * host-only context. */
+typedef struct gpudiff_cluster_index_stats {
+    uint64_t calls;         /* calls that returned an index */
+    uint64_t sorted_calls;  /* of those: the radix sort ran */
+    uint64_t syncs;         /* host synchronisations: at most 3 a call, 0 for a pass with nothing dirty */
+    uint64_t entries;       /* dirty entries indexed */
+    uint64_t d2h_bytes;     /* the packed blocks copied back */
+    double kernel_ms;
+    uint64_t timed_calls;
+} gpudiff_cluster_index_stats;
+int gpudiff_cluster_index_stats_get(gpudiff_ctx* ctx, gpudiff_cluster_index_stats* out);
+
 /* ---- device-resident object store (watch replay) ----
  * The informer cache's "old" objects stay resident in HBM, one per caller
  * slot (the shim maps (cluster, gvr, namespace, name) to a slot, as the

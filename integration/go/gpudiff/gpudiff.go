@@ -19,6 +19,7 @@ import (
 	"errors"
 	"fmt"
 	"math"
+	"sort"
 	"strconv"
 	"sync"
 	"time"
@@ -403,6 +404,55 @@ func (e *Engine) PathValues(res *C.gpudiff_result) [][]ChangedValue {
 		}
 	}
 	return out
+}
+
+// ClusterIndex is the per-cluster index of a waited pass's dirty IDs (gpudiff_cluster_index): logical cluster
+// ClusterIDs[j] owns SpecIDs[SpecOff[j]:SpecOff[j+1]] and StatusIDs[StatusOff[j]:StatusOff[j+1]], each in the batch's
+// order.  One consumer goroutine hands every listed cluster's syncer its two slices (INTEGRATION.md).
+type ClusterIndex struct {
+	ClusterIDs         []uint32 // ascending, distinct
+	SpecOff, StatusOff []uint32 // len(ClusterIDs) + 1
+	SpecIDs, StatusIDs []uint32
+	SortedOnDevice     bool // false: the dirty list was already in cluster order, no sort ran
+}
+
+// Of returns the spec-dirty and status-dirty pair IDs of one logical cluster (nil, nil when it is not listed).
+func (ci *ClusterIndex) Of(cluster uint32) (spec, status []uint32) {
+	j := sort.Search(len(ci.ClusterIDs), func(k int) bool { return ci.ClusterIDs[k] >= cluster })
+	if j == len(ci.ClusterIDs) || ci.ClusterIDs[j] != cluster {
+		return nil, nil
+	}
+	return ci.SpecIDs[ci.SpecOff[j]:ci.SpecOff[j+1]], ci.StatusIDs[ci.StatusOff[j]:ci.StatusOff[j+1]]
+}
+
+func copyU32(p *C.uint32_t, n int) []uint32 {
+	out := make([]uint32, n)
+	if n > 0 {
+		src := (*[1 << 28]C.uint32_t)(unsafe.Pointer(p))[:n:n]
+		for i := range out {
+			out[i] = uint32(src[i])
+		}
+	}
+	return out
+}
+
+// ClusterIndex builds the index of a waited ticket on the device (kernels K23 - K25) and copies it out before the
+// release: tickets of gpudiff_diff and of gpudiff_submit batches the engine encoded on the host; GPUDIFF_E_STATE for
+// an unwaited or superseded ticket and for device-encoded or store batches (gpudiff.h).
+func (e *Engine) ClusterIndex(ticket C.gpudiff_ticket) (*ClusterIndex, error) {
+	var ci C.gpudiff_cluster_index
+	e.mu.Lock()
+	defer e.mu.Unlock()
+	if err := errOf(C.gpudiff_cluster_index_get(e.ctx, ticket, &ci)); err != nil {
+		return nil, err
+	}
+	defer C.gpudiff_cluster_index_release(e.ctx, &ci)
+	nc := int(ci.n_clusters)
+	return &ClusterIndex{
+		ClusterIDs: copyU32(ci.cluster_ids, nc), SpecOff: copyU32(ci.spec_off, nc+1),
+		StatusOff: copyU32(ci.status_off, nc+1), SpecIDs: copyU32(ci.spec_ids, int(ci.n_spec)),
+		StatusIDs: copyU32(ci.status_ids, int(ci.n_status)), SortedOnDevice: ci.sorted_on_device != 0,
+	}, nil
 }
 
 func (b *Batcher) bytesHint(n int) int { return int(b.avgBytes*float64(n)*1.25) + 4096 }

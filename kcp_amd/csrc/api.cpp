@@ -209,6 +209,7 @@ void gpudiff_close(gpudiff_ctx* c) {
             (void)hipStreamDestroy(c->rb);
         }
         if (c->small_rb) (void)hipHostFree(c->small_rb);
+        if (c->fan) fan_ctx_release(c->fan);
         if (c->own_stream) (void)hipStreamDestroy(c->stream);
     }
     delete c;
@@ -863,6 +864,7 @@ int gpudiff_wait(gpudiff_ctx* c, gpudiff_ticket ticket, gpudiff_result* res) {
         c->finishers.erase(fin);
         if ((rc = fn(*rs))) return rc;
     }
+    d->waited = WaitedMark{ticket, (uint32_t)rs->spec.size(), (uint32_t)rs->status.size(), (uint32_t)rs->dirty.size()};
     res->n_pairs = rs->flags.size();
     res->pair_flags = rs->flags.data();
     res->n_spec_dirty = rs->spec.size();

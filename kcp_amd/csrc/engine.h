@@ -57,6 +57,17 @@ struct gpudiff_hbatch {
     hipEvent_t used = nullptr;  // last async copy that reads this batch
 };
 
+// gpudiff_cluster_index_get (fanout.cpp): the one mark gpudiff_wait leaves on a batch -- the ticket whose results it
+// returned and their counts -- and the index's device buffers, which live on the batch and grow on demand
+struct WaitedMark {
+    gpudiff_ticket ticket = 0;
+    uint32_t n_spec = 0, n_status = 0, n_dirty = 0;
+};
+struct FanBuffers;
+void fan_buffers_release(FanBuffers* f);
+struct FanCtx;
+void fan_ctx_release(FanCtx* f);
+
 struct gpudiff_dbatch {
     uint64_t pool_cap = 0, pool_used = 0;
     uint64_t max_pairs = 0, n_pairs = 0;
@@ -125,6 +136,8 @@ struct gpudiff_dbatch {
     // and whether the pass `done` stands for was a small one (collect_results reads the image then)
     uint8_t* small_image = nullptr;
     bool small_pending = false;
+    WaitedMark waited;          // set by gpudiff_wait alone; waited.ticket == ticket: the device arrays are final
+    FanBuffers* fan = nullptr;  // allocated by the batch's first gpudiff_cluster_index_get
 };
 
 struct DStore;
@@ -234,6 +247,7 @@ struct gpudiff_ctx {
     gpudiff_path_stats path_stats{};  // GPUDIFF_OPT_PATH_STRINGS: what the finishers rendered
     gpudiff_path_stats value_stats{};  // GPUDIFF_OPT_PATH_VALUES: the same, counted for the values
     uint64_t render_syncs = 0;  // stream synchronisations of the finishers' text rendering (gpudiff_render_syncs_get)
+    FanCtx* fan = nullptr;  // gpudiff_cluster_index_get: statistics, the pinned read-back buffer, events (first use)
     // submit ring
     gpudiff_dbatch* ring[2] = {nullptr, nullptr};
     gpudiff_hbatch* ring_hb[2] = {nullptr, nullptr};
@@ -274,6 +288,7 @@ inline void dfree_all(gpudiff_dbatch* d) {
     for (void* p : ps)
         if (p) (void)hipFree(p);
     if (d->done) (void)hipEventDestroy(d->done);
+    if (d->fan) fan_buffers_release(d->fan);
 }
 
 // copies a finished diff pass's results to host memory (gpudiff_wait's body)

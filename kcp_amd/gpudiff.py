@@ -308,6 +308,22 @@ class PassStats(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class ClusterIndexC(C.Structure):
+    _fields_ = [("n_clusters", C.c_size_t), ("cluster_ids", C.c_void_p), ("spec_off", C.c_void_p),
+                ("status_off", C.c_void_p), ("n_spec", C.c_size_t), ("n_status", C.c_size_t),
+                ("spec_ids", C.c_void_p), ("status_ids", C.c_void_p), ("sorted_on_device", C.c_uint32),
+                ("internal", C.c_void_p)]
+
+
+class ClusterIndexStats(C.Structure):
+    """gpudiff_cluster_index_stats: what the context's cluster_index calls cost since open."""
+    _fields_ = [("calls", C.c_uint64), ("sorted_calls", C.c_uint64), ("syncs", C.c_uint64), ("entries", C.c_uint64),
+                ("d2h_bytes", C.c_uint64), ("kernel_ms", C.c_double), ("timed_calls", C.c_uint64)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class DeviceView(C.Structure):
     _fields_ = [("pair_flags", C.c_void_p), ("spec_dirty_ids", C.c_void_p), ("status_dirty_ids", C.c_void_p),
                 ("dirty_ids", C.c_void_p), ("counts", C.c_void_p)]
@@ -369,6 +385,11 @@ SIGNATURES = [
     ("gpudiff_hbatch_resize", C.c_int, [_P, _P, C.c_uint64, C.c_size_t, C.c_uint64, C.POINTER(_P),
                                         C.POINTER(_P)]),
     ("gpudiff_submit", C.c_int, [_P, C.POINTER(JsonPair), C.c_size_t, C.POINTER(C.c_uint64)]),
+    ("gpudiff_cluster_index_get", C.c_int, [_P, C.c_uint64, C.POINTER(ClusterIndexC)]),
+    ("gpudiff_cluster_index_release", None, [_P, C.POINTER(ClusterIndexC)]),
+    ("gpudiff_cluster_index_host", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                             C.POINTER(ClusterIndexC)]),
+    ("gpudiff_cluster_index_stats_get", C.c_int, [_P, C.POINTER(ClusterIndexStats)]),
     ("gpudiff_store_create", C.c_int, [_P, C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(_P)]),
     ("gpudiff_store_create_ex", C.c_int, [_P, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(_P)]),
     ("gpudiff_store_submit", C.c_int, [_P, _P, C.POINTER(Event), C.c_size_t, C.POINTER(C.c_uint64)]),
@@ -578,6 +599,53 @@ def _arr(ptr, n, dtype):
         return np.zeros(0, dtype=dtype)
     ct = np.ctypeslib.as_ctypes_type(np.dtype(dtype))
     return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ct)), shape=(n,)).copy()
+
+
+@dataclass
+class ClusterIndex:
+    """Host copy of gpudiff_cluster_index: whose queue each dirty pair of a waited pass belongs to.  Cluster
+    cluster_ids[j] owns spec_ids[spec_off[j]:spec_off[j + 1]] and the like slice of status_ids; the ids of a slice
+    keep the batch's order."""
+    cluster_ids: np.ndarray   # u32 [n_clusters], ascending, distinct
+    spec_off: np.ndarray      # u32 [n_clusters + 1]
+    status_off: np.ndarray    # u32 [n_clusters + 1]
+    spec_ids: np.ndarray      # u32
+    status_ids: np.ndarray    # u32
+    sorted_on_device: int = 0  # 0: the dirty list was already in cluster order, no sort ran
+
+    def of(self, cluster_id: int) -> Tuple[np.ndarray, np.ndarray]:
+        """(spec_ids, status_ids) of one cluster, by binary search; two empty arrays for a cluster not listed."""
+        j = int(np.searchsorted(self.cluster_ids, np.uint32(cluster_id)))
+        if j >= self.cluster_ids.size or int(self.cluster_ids[j]) != int(cluster_id):
+            return self.spec_ids[:0], self.status_ids[:0]
+        return (self.spec_ids[int(self.spec_off[j]):int(self.spec_off[j + 1])],
+                self.status_ids[int(self.status_off[j]):int(self.status_off[j + 1])])
+
+
+def _take_cluster_index(ctx, ci: ClusterIndexC) -> ClusterIndex:
+    try:
+        return ClusterIndex(cluster_ids=_arr(ci.cluster_ids, ci.n_clusters, np.uint32),
+                            spec_off=_arr(ci.spec_off, ci.n_clusters + 1, np.uint32),
+                            status_off=_arr(ci.status_off, ci.n_clusters + 1, np.uint32),
+                            spec_ids=_arr(ci.spec_ids, ci.n_spec, np.uint32),
+                            status_ids=_arr(ci.status_ids, ci.n_status, np.uint32),
+                            sorted_on_device=int(ci.sorted_on_device))
+    finally:
+        _lib.gpudiff_cluster_index_release(ctx, C.byref(ci))
+
+
+def cluster_index_host(flags, pair_ids, cluster_ids) -> ClusterIndex:
+    """gpudiff_cluster_index_host: the index of rows given in batch order (final flags, pair ids, cluster ids), built on
+    one host thread -- the function Engine.cluster_index computes on the device."""
+    f = np.ascontiguousarray(flags, dtype=np.uint8)
+    p = np.ascontiguousarray(pair_ids, dtype=np.uint32)
+    c = np.ascontiguousarray(cluster_ids, dtype=np.uint32)
+    if not f.size == p.size == c.size:
+        raise ValueError("cluster_index_host: flags, pair_ids and cluster_ids differ in length")
+    ci = ClusterIndexC()
+    _chk(_lib.gpudiff_cluster_index_host(f.ctypes.data, p.ctypes.data, c.ctypes.data, f.size, C.byref(ci)),
+         "gpudiff_cluster_index_host")
+    return _take_cluster_index(None, ci)
 
 
 class HostBatch:
@@ -950,6 +1018,20 @@ class Engine:
         n = C.c_uint64(0)
         _chk(_lib.gpudiff_render_syncs_get(self.ctx, C.byref(n)), "gpudiff_render_syncs_get")
         return int(n.value)
+
+    def cluster_index(self, ticket: int) -> ClusterIndex:
+        """gpudiff_cluster_index_get: the per-cluster index of a waited ticket's dirty IDs, built on the device
+        (tickets of diff, and of submit on a context that encodes on the host; E_STATE otherwise)."""
+        ci = ClusterIndexC()
+        _chk(_lib.gpudiff_cluster_index_get(self.ctx, ticket, C.byref(ci)), "gpudiff_cluster_index_get")
+        return _take_cluster_index(self.ctx, ci)
+
+    def cluster_index_stats(self) -> ClusterIndexStats:
+        """gpudiff_cluster_index_stats_get: calls, sorted calls, host synchronisations, entries, bytes copied back
+        (kernel_ms with timing)."""
+        st = ClusterIndexStats()
+        _chk(_lib.gpudiff_cluster_index_stats_get(self.ctx, C.byref(st)), "gpudiff_cluster_index_stats_get")
+        return st
 
     def pass_stats(self) -> PassStats:
         """gpudiff_pass_stats_get: passes, fused small passes, the ones redone (by reason), read-back rounds."""
