@@ -124,7 +124,7 @@ int gpudiff_encode_objects(gpudiff_ctx* c, const uint8_t* const* docs, const siz
         td[i].json_len = (uint32_t)lens[i];
         td[i].scratch_off = sbytes;
         td[i].seed = seeds ? seeds[i] : 0u;
-        jbytes = (jbytes + lens[i] + kTokSlack + 15) & ~15ull;
+        jbytes += tok_staged_span(lens[i]);
         sbytes += tok_scratch_bytes(td[i].json_len);
     }
     jbytes += kTokSlack;

@@ -262,6 +262,17 @@ inline gd::WorkerPool& workers(gpudiff_ctx* c) {
     return *c->pool;
 }
 
+// the host path of the n_def documents a kernel deferred: fn(k) for k in [0, n_def), strided over one of the
+// context's threads per 64 of them
+template <class F>
+inline void for_deferred(gpudiff_ctx* c, size_t n_def, F&& fn) {
+    if (!n_def) return;
+    const uint32_t T = std::max<uint32_t>(1, std::min<uint32_t>(c->threads, (uint32_t)((n_def + 63) / 64)));
+    workers(c).run(T, [&](uint32_t t) {
+        for (size_t k = t; k < n_def; k += T) fn(k);
+    });
+}
+
 inline int set_device(gpudiff_ctx* c) {
     if (!c->has_device) return GPUDIFF_E_NODEVICE;
     HIPCHK(hipSetDevice(c->device));

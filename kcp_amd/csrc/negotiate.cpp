@@ -23,26 +23,21 @@
 #include <thread>
 #include <vector>
 
+#include "doc_batch.h"
 #include "engine.h"
 #include "goscan.h"
 #include "tokenize.h"
 
 using namespace gd;
 
-struct gpudiff_nbatch {
+struct gpudiff_nbatch : DocBatch {  // docs: 2 per pair, old then new
     uint32_t n = 0;
-    std::vector<TokDoc> docs;  // 2 per pair: old, new
     std::vector<const uint8_t*> olds, news;
     std::vector<size_t> old_lens, new_lens;
     std::vector<uint8_t> kinds;  // GPUDIFF_NEG_KIND_* per pair
-    uint64_t json_bytes = 0, scratch_bytes = 0, n_host = 0;
+    uint64_t n_host = 0;
     bool ran = false;  // a run was issued (fetch before any run: GPUDIFF_E_STATE)
-    void *d_json = nullptr, *d_scratch = nullptr, *d_docs = nullptr, *d_no = nullptr, *d_absent = nullptr,
-         *d_act = nullptr;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    bool pending_timing = false;
-    double k13_ms_sum = 0, k14_ms_sum = 0;
-    uint64_t runs = 0;
+    void *d_no = nullptr, *d_absent = nullptr, *d_act = nullptr;
 };
 
 namespace {
@@ -403,27 +398,6 @@ int32_t classify_host(const uint8_t* a, size_t al, const uint8_t* b, size_t bl, 
     return GPUDIFF_NEG_IGNORE;
 }
 
-void free_nbatch(gpudiff_nbatch* nb) {
-    if (!nb) return;
-    void* ptrs[] = {nb->d_json, nb->d_scratch, nb->d_docs, nb->d_no, nb->d_absent, nb->d_act};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    for (hipEvent_t& e : nb->ev)
-        if (e) (void)hipEventDestroy(e);
-    delete nb;
-}
-
-void fold_timing(gpudiff_nbatch* nb) {
-    float a = 0, b = 0;
-    if (hipEventElapsedTime(&a, nb->ev[0], nb->ev[1]) == hipSuccess &&
-        hipEventElapsedTime(&b, nb->ev[1], nb->ev[2]) == hipSuccess) {
-        nb->k13_ms_sum += a;
-        nb->k14_ms_sum += b;
-        nb->runs++;
-    }
-    nb->pending_timing = false;
-}
-
 }  // namespace
 
 extern "C" {
@@ -472,7 +446,7 @@ int gpudiff_nbatch_create_kinds(gpudiff_ctx* c, const uint8_t* kinds, const uint
         if ((!news[i] && new_lens[i]) || (kinds && kinds[i] > GPUDIFF_NEG_KIND_CRD)) return GPUDIFF_E_INVAL;
     int rc = set_device(c);
     if (rc) return rc;
-    gpudiff_nbatch* nb = new (std::nothrow) gpudiff_nbatch();
+    std::unique_ptr<gpudiff_nbatch> nb(new (std::nothrow) gpudiff_nbatch());
     if (!nb) return GPUDIFF_E_NOMEM;
     nb->n = (uint32_t)n;
     nb->olds.assign(olds, olds + n);
@@ -482,60 +456,21 @@ int gpudiff_nbatch_create_kinds(gpudiff_ctx* c, const uint8_t* kinds, const uint
     if (kinds) nb->kinds.assign(kinds, kinds + n);
     else nb->kinds.assign(n, (uint8_t)GPUDIFF_NEG_KIND_API);
     nb->docs.resize(2 * n);
-    std::vector<uint8_t> absent(n, 0);
-    uint64_t jb = 0, sb = 0;
-    for (size_t i = 0; i < 2 * n; i++) {
-        const size_t p = i / 2;
-        const bool is_old = (i & 1) == 0;
-        if (is_old && !olds[p]) absent[p] = 1;
-        const size_t raw = is_old ? (olds[p] ? old_lens[p] : 0) : new_lens[p];
-        const uint32_t l = raw > kTokMaxLen ? kTokMaxLen + 1 : (uint32_t)raw;
-        TokDoc& t = nb->docs[i];
-        memset(&t, 0, sizeof(t));
-        t.json_off = jb;
-        t.json_len = l;
-        t.scratch_off = sb;
-        tokdoc_set_neg_kind(t, nb->kinds[p]);  // K13: which typed status to read
-        if (l <= kTokMaxLen) {
-            jb = (jb + l + kTokSlack + 15) & ~15ull;
-            sb += rollup_scratch_bytes(l);
-        }
-    }
-    jb += kTokSlack;
-    nb->json_bytes = jb;
-    nb->scratch_bytes = sb;
-    auto fail = [&](hipError_t e) {
-        free_nbatch(nb);
-        return e == hipErrorOutOfMemory ? GPUDIFF_E_CAPACITY : GPUDIFF_E_DEVICE;
-    };
-    hipError_t e;
-    const size_t nd = std::max<size_t>(2 * n, 1);
-    if ((e = hipMalloc(&nb->d_json, jb)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&nb->d_scratch, std::max<uint64_t>(sb, 256))) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&nb->d_docs, nd * sizeof(TokDoc))) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&nb->d_no, nd * sizeof(NegOut))) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&nb->d_absent, std::max<size_t>(n, 1))) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&nb->d_act, std::max<size_t>(n, 1) * 4)) != hipSuccess) return fail(e);
-    void* stage = nullptr;
-    if ((e = hipHostMalloc(&stage, jb, hipHostMallocDefault)) != hipSuccess) return fail(e);
-    memset(stage, 0, jb);
-    for (size_t i = 0; i < 2 * n; i++) {
-        const size_t p = i / 2;
-        const uint8_t* src = (i & 1) ? news[p] : olds[p];
-        const TokDoc& t = nb->docs[i];
-        if (src && t.json_len && t.json_len <= kTokMaxLen) memcpy((uint8_t*)stage + t.json_off, src, t.json_len);
-    }
-    e = hipMemcpyAsync(nb->d_json, stage, jb, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && n)
-        e = hipMemcpyAsync(nb->d_docs, nb->docs.data(), 2 * n * sizeof(TokDoc), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && n) e = hipMemcpyAsync(nb->d_absent, absent.data(), n, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipHostFree(stage);
-    if (e != hipSuccess) return fail(e);
-    if (c->flags & GPUDIFF_OPT_TIMING)
-        for (hipEvent_t& ev : nb->ev)
-            if ((e = hipEventCreate(&ev)) != hipSuccess) return fail(e);
-    *out = nb;
+    std::vector<uint8_t> absent(n);
+    for (size_t p = 0; p < n; p++) absent[p] = olds[p] ? 0 : 1;
+    // document 2p is pair p's old object (absent: an empty document), 2p + 1 its new one
+    const DocTableBytes B = lay_out_docs(
+        nb->docs.data(), 2 * n,
+        [&](size_t i) { return (i & 1) ? new_lens[i / 2] : (olds[i / 2] ? old_lens[i / 2] : 0); },
+        rollup_scratch_bytes, nullptr,
+        [&](size_t i, TokDoc& t, uint64_t) { tokdoc_set_neg_kind(t, nb->kinds[i / 2]); });  // K13: which typed status
+    if ((rc = nb->alloc(&nb->d_no, std::max<size_t>(2 * n, 1) * sizeof(NegOut)))) return rc;
+    if ((rc = nb->alloc(&nb->d_absent, std::max<size_t>(n, 1)))) return rc;
+    if ((rc = nb->alloc(&nb->d_act, std::max<size_t>(n, 1) * 4))) return rc;
+    if ((rc = nb->upload(c, B, [&](size_t i) { return (i & 1) ? news[i / 2] : olds[i / 2]; }, 3,
+                         {nb->d_absent, absent.data(), n})))
+        return rc;
+    *out = nb.release();
     return GPUDIFF_OK;
 }
 
@@ -543,20 +478,14 @@ int gpudiff_nbatch_run(gpudiff_ctx* c, gpudiff_nbatch* nb) {
     if (!c || !nb) return GPUDIFF_E_INVAL;
     int rc = set_device(c);
     if (rc) return rc;
-    if (nb->pending_timing) {
-        HIPCHK(hipEventSynchronize(nb->ev[2]));
-        fold_timing(nb);
-    }
-    if (nb->ev[0]) HIPCHK(hipEventRecord(nb->ev[0], c->stream));
+    if ((rc = nb->await_timing())) return rc;
+    if ((rc = nb->record(c, 0))) return rc;
     HIPCHK(launch_negotiate_docs(c->stream, (const TokDoc*)nb->d_docs, 2 * nb->n, (const uint8_t*)nb->d_json,
                                  (uint8_t*)nb->d_scratch, (NegOut*)nb->d_no));
-    if (nb->ev[1]) HIPCHK(hipEventRecord(nb->ev[1], c->stream));
+    if ((rc = nb->record(c, 1))) return rc;
     HIPCHK(launch_negotiate_pairs(c->stream, (const NegOut*)nb->d_no, (const uint8_t*)nb->d_absent,
                                   (const TokDoc*)nb->d_docs, (const uint8_t*)nb->d_json, nb->n, (int32_t*)nb->d_act));
-    if (nb->ev[2]) {
-        HIPCHK(hipEventRecord(nb->ev[2], c->stream));
-        nb->pending_timing = true;
-    }
+    if ((rc = nb->record(c, 2))) return rc;
     nb->ran = true;
     return GPUDIFF_OK;
 }
@@ -569,21 +498,16 @@ int gpudiff_nbatch_fetch(gpudiff_ctx* c, gpudiff_nbatch* nb, int32_t* actions) {
     const size_t n = nb->n;
     if (n) HIPCHK(hipMemcpyAsync(actions, nb->d_act, n * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    if (nb->pending_timing) fold_timing(nb);
+    nb->fold_timing();
     std::vector<uint32_t> def;
     for (size_t i = 0; i < n; i++)
         if (actions[i] == kNegDefer) def.push_back((uint32_t)i);
     nb->n_host = def.size();
-    if (def.empty()) return GPUDIFF_OK;
     // the host path for the deferred pairs, on the context's encode threads
-    const uint32_t T = std::max<uint32_t>(1, std::min<uint32_t>(c->threads, (uint32_t)((def.size() + 63) / 64)));
-    auto work = [&](uint32_t t) {
-        for (size_t k = t; k < def.size(); k += T) {
-            const uint32_t i = def[k];
-            actions[i] = classify_host(nb->olds[i], nb->old_lens[i], nb->news[i], nb->new_lens[i], nb->kinds[i]);
-        }
-    };
-    workers(c).run(T, work);
+    for_deferred(c, def.size(), [&](size_t k) {
+        const uint32_t i = def[k];
+        actions[i] = classify_host(nb->olds[i], nb->old_lens[i], nb->news[i], nb->new_lens[i], nb->kinds[i]);
+    });
     return GPUDIFF_OK;
 }
 
@@ -595,18 +519,15 @@ int gpudiff_nbatch_stats_get(const gpudiff_nbatch* nb, gpudiff_nbatch_stats* st)
     st->scratch_bytes = nb->scratch_bytes + 2ull * nb->n * sizeof(NegOut);
     st->n_host = nb->n_host;
     st->runs = nb->runs;
-    st->k13_ms = nb->runs ? nb->k13_ms_sum / (double)nb->runs : 0.0;
-    st->k14_ms = nb->runs ? nb->k14_ms_sum / (double)nb->runs : 0.0;
+    st->k13_ms = nb->mean_ms(0);
+    st->k14_ms = nb->mean_ms(1);
     return GPUDIFF_OK;
 }
 
 void gpudiff_nbatch_free(gpudiff_ctx* c, gpudiff_nbatch* nb) {
     if (!nb) return;
-    if (c && c->has_device) {
-        (void)hipSetDevice(c->device);
-        (void)hipStreamSynchronize(c->stream);
-    }
-    free_nbatch(nb);
+    doc_batch_quiesce(c);
+    delete nb;
 }
 
 int gpudiff_nbatch_create(gpudiff_ctx* c, const uint8_t* const* olds, const size_t* old_lens,

@@ -26,6 +26,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "doc_batch.h"
 #include "engine.h"
 #include "goscan.h"
 #include "rollup.h"
@@ -33,18 +34,12 @@
 
 using namespace gd;
 
-struct gpudiff_rbatch {
+struct gpudiff_rbatch : DocBatch {
     uint32_t n = 0;
-    std::vector<TokDoc> docs;
     std::vector<const uint8_t*> src;
     std::vector<size_t> lens;
-    uint64_t json_bytes = 0, scratch_bytes = 0;
-    void *d_json = nullptr, *d_scratch = nullptr, *d_docs = nullptr, *d_ro = nullptr, *d_grp = nullptr;
+    void *d_ro = nullptr, *d_grp = nullptr;
     RollGroupBufs B{};
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    bool pending_timing = false;
-    double k11_ms_sum = 0, k12_ms_sum = 0;
-    uint64_t runs = 0;
 };
 
 namespace {
@@ -164,27 +159,6 @@ void publish(RollupStore* rs, gpudiff_rollup* out, size_t n, size_t n_host, uint
 
 inline int32_t wrap_add(int32_t a, int32_t b) { return (int32_t)((uint32_t)a + (uint32_t)b); }
 
-void free_rbatch(gpudiff_rbatch* rb) {
-    if (!rb) return;
-    void* ptrs[] = {rb->d_json, rb->d_scratch, rb->d_docs, rb->d_ro, rb->d_grp};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    for (hipEvent_t& e : rb->ev)
-        if (e) (void)hipEventDestroy(e);
-    delete rb;
-}
-
-void fold_timing(gpudiff_rbatch* rb) {
-    float a = 0, b = 0;
-    if (hipEventElapsedTime(&a, rb->ev[0], rb->ev[1]) == hipSuccess &&
-        hipEventElapsedTime(&b, rb->ev[1], rb->ev[2]) == hipSuccess) {
-        rb->k11_ms_sum += a;
-        rb->k12_ms_sum += b;
-        rb->runs++;
-    }
-    rb->pending_timing = false;
-}
-
 }  // namespace
 
 extern "C" {
@@ -214,56 +188,20 @@ int gpudiff_rbatch_create(gpudiff_ctx* c, const uint8_t* const* docs, const size
     *out = nullptr;
     int rc = set_device(c);
     if (rc) return rc;
-    gpudiff_rbatch* rb = new (std::nothrow) gpudiff_rbatch();
+    std::unique_ptr<gpudiff_rbatch> rb(new (std::nothrow) gpudiff_rbatch());
     if (!rb) return GPUDIFF_E_NOMEM;
     rb->n = (uint32_t)n;
     rb->docs.resize(n);
     rb->src.assign(docs, docs + n);
     rb->lens.assign(lens, lens + n);
-    uint64_t jb = 0, sb = 0;
-    for (size_t i = 0; i < n; i++) {
-        // documents beyond the size limit still get a TokDoc: K11 reports GPUDIFF_TOK_SIZE
-        const uint32_t l = lens[i] > kTokMaxLen ? kTokMaxLen + 1 : (uint32_t)lens[i];
-        TokDoc& t = rb->docs[i];
-        memset(&t, 0, sizeof(t));
-        t.json_off = jb;
-        t.json_len = l;
-        t.scratch_off = sb;
-        if (l <= kTokMaxLen) {
-            jb = (jb + l + kTokSlack + 15) & ~15ull;
-            sb += rollup_scratch_bytes(l);
-        }
-    }
-    jb += kTokSlack;
-    rb->json_bytes = jb;
-    rb->scratch_bytes = sb;
-    const RollGroupBufs L = rollup_group_layout(nullptr, rb->n);
-    auto fail = [&](hipError_t e) {
-        free_rbatch(rb);
-        return e == hipErrorOutOfMemory ? GPUDIFF_E_CAPACITY : GPUDIFF_E_DEVICE;
-    };
-    hipError_t e;
-    if ((e = hipMalloc(&rb->d_json, jb)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&rb->d_scratch, std::max<uint64_t>(sb, 256))) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&rb->d_docs, std::max<size_t>(n, 1) * sizeof(TokDoc))) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&rb->d_ro, std::max<size_t>(n, 1) * sizeof(RollOut))) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&rb->d_grp, L.total)) != hipSuccess) return fail(e);
+    const DocTableBytes B = lay_out_docs(
+        rb->docs.data(), n, [&](size_t i) { return lens[i]; }, rollup_scratch_bytes, nullptr,
+        [](size_t, TokDoc&, uint64_t) {});
+    if ((rc = rb->alloc(&rb->d_ro, std::max<size_t>(n, 1) * sizeof(RollOut)))) return rc;
+    if ((rc = rb->alloc(&rb->d_grp, rollup_group_layout(nullptr, rb->n).total))) return rc;
     rb->B = rollup_group_layout((uint8_t*)rb->d_grp, rb->n);
-    void* stage = nullptr;
-    if ((e = hipHostMalloc(&stage, jb, hipHostMallocDefault)) != hipSuccess) return fail(e);
-    memset(stage, 0, jb);
-    for (size_t i = 0; i < n; i++)
-        if (rb->docs[i].json_len <= kTokMaxLen && lens[i]) memcpy((uint8_t*)stage + rb->docs[i].json_off, docs[i], lens[i]);
-    e = hipMemcpyAsync(rb->d_json, stage, jb, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && n)
-        e = hipMemcpyAsync(rb->d_docs, rb->docs.data(), n * sizeof(TokDoc), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipHostFree(stage);
-    if (e != hipSuccess) return fail(e);
-    if (c->flags & GPUDIFF_OPT_TIMING)
-        for (hipEvent_t& ev : rb->ev)
-            if ((e = hipEventCreate(&ev)) != hipSuccess) return fail(e);
-    *out = rb;
+    if ((rc = rb->upload(c, B, [&](size_t i) { return docs[i]; }, 3))) return rc;
+    *out = rb.release();
     return GPUDIFF_OK;
 }
 
@@ -271,21 +209,14 @@ int gpudiff_rbatch_run(gpudiff_ctx* c, gpudiff_rbatch* rb) {
     if (!c || !rb) return GPUDIFF_E_INVAL;
     int rc = set_device(c);
     if (rc) return rc;
-    if (rb->pending_timing) {
-        HIPCHK(hipEventSynchronize(rb->ev[2]));
-        fold_timing(rb);
-    }
-    if (rb->ev[0]) HIPCHK(hipEventRecord(rb->ev[0], c->stream));
+    if ((rc = rb->await_timing())) return rc;
+    if ((rc = rb->record(c, 0))) return rc;
     HIPCHK(launch_rollup_docs(c->stream, (const TokDoc*)rb->d_docs, rb->n, (const uint8_t*)rb->d_json,
                               (uint8_t*)rb->d_scratch, (RollOut*)rb->d_ro));
-    if (rb->ev[1]) HIPCHK(hipEventRecord(rb->ev[1], c->stream));
+    if ((rc = rb->record(c, 1))) return rc;
     HIPCHK(launch_rollup_group(c->stream, (const RollOut*)rb->d_ro, (const TokDoc*)rb->d_docs,
                                (const uint8_t*)rb->d_json, rb->n, rb->B));
-    if (rb->ev[2]) {
-        HIPCHK(hipEventRecord(rb->ev[2], c->stream));
-        rb->pending_timing = true;
-    }
-    return GPUDIFF_OK;
+    return rb->record(c, 2);
 }
 
 int gpudiff_rbatch_fetch(gpudiff_ctx* c, gpudiff_rbatch* rb, gpudiff_rollup* out) {
@@ -296,21 +227,16 @@ int gpudiff_rbatch_fetch(gpudiff_ctx* c, gpudiff_rbatch* rb, gpudiff_rollup* out
     const size_t n = rb->n;
     std::vector<RollOut> ro(n);
     uint32_t counts[2] = {0, 0};
-    RollupStore* rs = new (std::nothrow) RollupStore();
+    std::unique_ptr<RollupStore> rs(new (std::nothrow) RollupStore());
     if (!rs) return GPUDIFF_E_NOMEM;
     rs->doc_group.resize(n);
-    auto bail = [&](hipError_t) {
-        delete rs;
-        return GPUDIFF_E_DEVICE;
-    };
-    hipError_t e = hipSuccess;
-    if (n) e = hipMemcpyAsync(ro.data(), rb->d_ro, n * sizeof(RollOut), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess && n)
-        e = hipMemcpyAsync(rs->doc_group.data(), rb->B.doc_group, n * 4, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(counts, rb->B.counts, 8, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return bail(e);
-    if (rb->pending_timing) fold_timing(rb);
+    if (n) {
+        HIPCHK(hipMemcpyAsync(ro.data(), rb->d_ro, n * sizeof(RollOut), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(rs->doc_group.data(), rb->B.doc_group, n * 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(hipMemcpyAsync(counts, rb->B.counts, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    rb->fold_timing();
     rs->k11.resize(n);
     std::vector<uint32_t> def;
     for (size_t i = 0; i < n; i++) {
@@ -321,20 +247,15 @@ int gpudiff_rbatch_fetch(gpudiff_ctx* c, gpudiff_rbatch* rb, gpudiff_rollup* out
     if (!regroup) {
         rs->groups.resize(counts[0]);
         if (counts[0])
-            e = hipMemcpy(rs->groups.data(), rb->B.groups, counts[0] * sizeof(gpudiff_rollup_group),
-                          hipMemcpyDeviceToHost);
-        if (e != hipSuccess) return bail(e);
-        publish(rs, out, n, 0, 0);
+            HIPCHK(hipMemcpy(rs->groups.data(), rb->B.groups, counts[0] * sizeof(gpudiff_rollup_group),
+                             hipMemcpyDeviceToHost));
+        publish(rs.release(), out, n, 0, 0);
         return GPUDIFF_OK;
     }
     // the host path for the deferred documents, on the context's encode threads
     std::vector<Fields> hf(def.size());
     std::vector<uint8_t> hok(def.size(), 0);
-    const uint32_t T = std::max<uint32_t>(1, std::min<uint32_t>(c->threads, (uint32_t)((def.size() + 63) / 64)));
-    auto work = [&](uint32_t t) {
-        for (size_t k = t; k < def.size(); k += T) hok[k] = host_fields(rb->src[def[k]], rb->lens[def[k]], hf[k]);
-    };
-    workers(c).run(T, work);
+    for_deferred(c, def.size(), [&](size_t k) { hok[k] = host_fields(rb->src[def[k]], rb->lens[def[k]], hf[k]); });
     // exact regrouping in document order (first appearance = ascending first_doc)
     std::unordered_map<std::string, int32_t> index;
     index.reserve(counts[0] + def.size());
@@ -372,7 +293,7 @@ int gpudiff_rbatch_fetch(gpudiff_ctx* c, gpudiff_rbatch* rb, gpudiff_rollup* out
         for (int f = 0; f < 5; f++) g.sums[f] = wrap_add(g.sums[f], v[f]);
         rs->doc_group[i] = it.first->second;
     }
-    publish(rs, out, n, def.size(), 1);
+    publish(rs.release(), out, n, def.size(), 1);
     return GPUDIFF_OK;
 }
 
@@ -383,18 +304,15 @@ int gpudiff_rbatch_stats_get(const gpudiff_rbatch* rb, gpudiff_rbatch_stats* st)
     for (size_t l : rb->lens) st->json_bytes += l;
     st->scratch_bytes = rb->scratch_bytes + rb->B.total;
     st->runs = rb->runs;
-    st->k11_ms = rb->runs ? rb->k11_ms_sum / (double)rb->runs : 0.0;
-    st->k12_ms = rb->runs ? rb->k12_ms_sum / (double)rb->runs : 0.0;
+    st->k11_ms = rb->mean_ms(0);
+    st->k12_ms = rb->mean_ms(1);
     return GPUDIFF_OK;
 }
 
 void gpudiff_rbatch_free(gpudiff_ctx* c, gpudiff_rbatch* rb) {
     if (!rb) return;
-    if (c && c->has_device) {
-        (void)hipSetDevice(c->device);
-        (void)hipStreamSynchronize(c->stream);
-    }
-    free_rbatch(rb);
+    doc_batch_quiesce(c);
+    delete rb;
 }
 
 int gpudiff_rollup_status(gpudiff_ctx* c, const uint8_t* const* docs, const size_t* lens, size_t n,

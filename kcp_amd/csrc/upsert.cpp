@@ -24,6 +24,7 @@
 #include <thread>
 #include <vector>
 
+#include "doc_batch.h"
 #include "dstore.h"
 #include "engine.h"
 #include "json.h"
@@ -302,17 +303,12 @@ void upsert_body(const Node& root, uint32_t mode, std::string& o) {
 }  // namespace gd
 
 // ------------------------------------------------------------------ C-ABI
-struct gpudiff_wbatch {
+struct gpudiff_wbatch : DocBatch {
     uint32_t n = 0, mode = 0;
-    std::vector<TokDoc> docs;
     std::vector<const uint8_t*> src;
     std::vector<size_t> lens;
-    uint64_t json_bytes = 0, scratch_bytes = 0, out_bytes = 0;
-    void *d_json = nullptr, *d_scratch = nullptr, *d_out = nullptr, *d_docs = nullptr, *d_res = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    bool pending_timing = false;
-    double k10_ms_sum = 0;
-    uint64_t runs = 0, body_bytes = 0;
+    uint64_t out_bytes = 0, body_bytes = 0;
+    void *d_out = nullptr, *d_res = nullptr;
 };
 
 namespace {
@@ -335,12 +331,34 @@ void publish(BodiesStore* bs, gpudiff_bodies* out, size_t n, size_t n_host) {
     out->internal = bs;
 }
 
-void free_wbatch(gpudiff_wbatch* wb) {
-    for (void* p : {wb->d_json, wb->d_scratch, wb->d_out, wb->d_docs, wb->d_res})
-        if (p) (void)hipFree(p);
-    for (hipEvent_t e : wb->ev)
-        if (e) (void)hipEventDestroy(e);
-    delete wb;
+// One write's body, as assemble_bodies takes it: the device's bytes, the host's, a Go decode error on the host
+// path, or none at all (a no-op write)
+struct Body {
+    enum Kind { kNone, kDevice, kHost, kDecodeError } kind;
+    const uint8_t* p;
+    size_t n;
+};
+
+// offsets / bytes / status / source of bs for nw writes.  body_of(w) is called exactly once per write, for
+// w = 0, 1, ..., nw - 1 in that order: the callers' lambdas count deferred writes and fill bs->k10 as they go
+template <class F>
+void assemble_bodies(BodiesStore* bs, size_t nw, F&& body_of) {
+    bs->offsets.resize(nw + 1);
+    bs->status.assign(nw, 0);
+    bs->source.assign(nw, GPUDIFF_BODY_DEVICE);
+    for (size_t w = 0; w < nw; w++) {
+        bs->offsets[w] = bs->bytes.size();
+        const Body b = body_of(w);
+        if (b.kind == Body::kHost || b.kind == Body::kDecodeError) bs->source[w] = GPUDIFF_BODY_HOST;
+        if (b.kind == Body::kDecodeError) bs->status[w] = GPUDIFF_E_DECODE;
+        else if (b.kind != Body::kNone) bs->bytes.insert(bs->bytes.end(), b.p, b.p + b.n);
+    }
+    bs->offsets[nw] = bs->bytes.size();
+}
+
+// the host path's answer for one deferred write
+Body host_body_of(const std::string& body, bool ok) {
+    return ok ? Body{Body::kHost, (const uint8_t*)body.data(), body.size()} : Body{Body::kDecodeError, nullptr, 0};
 }
 
 // host marshal of one document into o; false = Go decode error
@@ -378,60 +396,21 @@ int gpudiff_wbatch_create(gpudiff_ctx* c, const uint8_t* const* docs, const size
     *out = nullptr;
     int rc = set_device(c);
     if (rc) return rc;
-    gpudiff_wbatch* wb = new (std::nothrow) gpudiff_wbatch();
+    std::unique_ptr<gpudiff_wbatch> wb(new (std::nothrow) gpudiff_wbatch());
     if (!wb) return GPUDIFF_E_NOMEM;
     wb->n = (uint32_t)n;
     wb->mode = mode;
     wb->docs.resize(n);
     wb->src.assign(docs, docs + n);
     wb->lens.assign(lens, lens + n);
-    uint64_t jb = 0, sb = 0, ob = 0;
-    for (size_t i = 0; i < n; i++) {
-        // documents beyond K10's size limit still get a TokDoc: the kernel reports GPUDIFF_TOK_SIZE
-        const uint32_t l = lens[i] > kTokMaxLen ? kTokMaxLen + 1 : (uint32_t)lens[i];
-        TokDoc& t = wb->docs[i];
-        memset(&t, 0, sizeof(t));
-        t.json_off = jb;
-        t.json_len = l;
-        t.scratch_off = sb;
-        tokdoc_set_marshal_off(t, ob);
-        if (l <= kTokMaxLen) {
-            jb = (jb + l + kTokSlack + 15) & ~15ull;
-            sb += marshal_scratch_bytes(l);
-            ob += marshal_out_cap(l);
-        }
-    }
-    jb += kTokSlack;
-    wb->json_bytes = jb;
-    wb->scratch_bytes = sb;
-    wb->out_bytes = ob;
-    auto fail = [&](hipError_t e) {
-        free_wbatch(wb);
-        return e == hipErrorOutOfMemory ? GPUDIFF_E_CAPACITY : GPUDIFF_E_DEVICE;
-    };
-    hipError_t e;
-    if ((e = hipMalloc(&wb->d_json, jb)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&wb->d_scratch, std::max<uint64_t>(sb, 256))) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&wb->d_out, std::max<uint64_t>(ob, 256))) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&wb->d_docs, std::max<size_t>(n, 1) * sizeof(TokDoc))) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&wb->d_res, std::max<size_t>(n, 1) * sizeof(TokOut))) != hipSuccess) return fail(e);
-    // JSON up through one pinned staging buffer
-    void* stage = nullptr;
-    if ((e = hipHostMalloc(&stage, jb, hipHostMallocDefault)) != hipSuccess) return fail(e);
-    memset(stage, 0, jb);
-    for (size_t i = 0; i < n; i++)
-        if (wb->docs[i].json_len <= kTokMaxLen && lens[i]) memcpy((uint8_t*)stage + wb->docs[i].json_off, docs[i], lens[i]);
-    e = hipMemcpyAsync(wb->d_json, stage, jb, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && n)
-        e = hipMemcpyAsync(wb->d_docs, wb->docs.data(), n * sizeof(TokDoc), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipHostFree(stage);
-    if (e != hipSuccess) return fail(e);
-    if (c->flags & GPUDIFF_OPT_TIMING) {
-        if ((e = hipEventCreate(&wb->ev[0])) != hipSuccess) return fail(e);
-        if ((e = hipEventCreate(&wb->ev[1])) != hipSuccess) return fail(e);
-    }
-    *out = wb;
+    const DocTableBytes B = lay_out_docs(
+        wb->docs.data(), n, [&](size_t i) { return lens[i]; }, marshal_scratch_bytes, marshal_out_cap,
+        [](size_t, TokDoc& t, uint64_t out_off) { tokdoc_set_marshal_off(t, out_off); });
+    wb->out_bytes = B.out_bytes;
+    if ((rc = wb->alloc(&wb->d_out, std::max<uint64_t>(B.out_bytes, 256)))) return rc;
+    if ((rc = wb->alloc(&wb->d_res, std::max<size_t>(n, 1) * sizeof(TokOut)))) return rc;
+    if ((rc = wb->upload(c, B, [&](size_t i) { return docs[i]; }, 2))) return rc;
+    *out = wb.release();
     return GPUDIFF_OK;
 }
 
@@ -439,22 +418,11 @@ int gpudiff_wbatch_run(gpudiff_ctx* c, gpudiff_wbatch* wb) {
     if (!c || !wb) return GPUDIFF_E_INVAL;
     int rc = set_device(c);
     if (rc) return rc;
-    if (wb->pending_timing) {  // fold the previous run's duration in
-        float ms = 0;
-        HIPCHK(hipEventSynchronize(wb->ev[1]));
-        HIPCHK(hipEventElapsedTime(&ms, wb->ev[0], wb->ev[1]));
-        wb->k10_ms_sum += ms;
-        wb->runs++;
-        wb->pending_timing = false;
-    }
-    if (wb->ev[0]) HIPCHK(hipEventRecord(wb->ev[0], c->stream));
+    if ((rc = wb->await_timing())) return rc;  // the previous run's duration
+    if ((rc = wb->record(c, 0))) return rc;
     HIPCHK(launch_marshal_docs(c->stream, (const TokDoc*)wb->d_docs, wb->n, (const uint8_t*)wb->d_json,
                                (uint8_t*)wb->d_scratch, (uint8_t*)wb->d_out, wb->mode, (TokOut*)wb->d_res));
-    if (wb->ev[1]) {
-        HIPCHK(hipEventRecord(wb->ev[1], c->stream));
-        wb->pending_timing = true;
-    }
-    return GPUDIFF_OK;
+    return wb->record(c, 1);
 }
 
 int gpudiff_wbatch_fetch(gpudiff_ctx* c, gpudiff_wbatch* wb, gpudiff_bodies* out) {
@@ -468,51 +436,32 @@ int gpudiff_wbatch_fetch(gpudiff_ctx* c, gpudiff_wbatch* wb, gpudiff_bodies* out
     if (n) HIPCHK(hipMemcpyAsync(to.data(), wb->d_res, n * sizeof(TokOut), hipMemcpyDeviceToHost, c->stream));
     if (wb->out_bytes) HIPCHK(hipMemcpyAsync(raw.data(), wb->d_out, wb->out_bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    if (wb->pending_timing) {
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, wb->ev[0], wb->ev[1]));
-        wb->k10_ms_sum += ms;
-        wb->runs++;
-        wb->pending_timing = false;
-    }
+    wb->fold_timing();
     BodiesStore* bs = new (std::nothrow) BodiesStore();
     if (!bs) return GPUDIFF_E_NOMEM;
-    bs->offsets.resize(n + 1);
-    bs->status.assign(n, 0);
-    bs->k10.resize(n);
-    bs->source.assign(n, GPUDIFF_BODY_DEVICE);
     // documents K10 left: the host path, on the context's encode threads
     std::vector<uint32_t> def;
     for (size_t i = 0; i < n; i++)
         if (to[i].status != GPUDIFF_TOK_OK) def.push_back((uint32_t)i);
     std::vector<std::string> hb(def.size());
     std::vector<uint8_t> hok(def.size(), 0);
-    const uint32_t T = std::max<uint32_t>(1, std::min<uint32_t>(c->threads, (uint32_t)((def.size() + 63) / 64)));
-    auto work = [&](uint32_t t) {
-        for (size_t k = t; k < def.size(); k += T)
-            hok[k] = host_body(wb->src[def[k]], wb->lens[def[k]], wb->mode, hb[k]) ? 1 : 0;
-    };
-    workers(c).run(T, work);
-    const size_t n_host = def.size();
+    for_deferred(c, def.size(), [&](size_t k) {
+        hok[k] = host_body(wb->src[def[k]], wb->lens[def[k]], wb->mode, hb[k]) ? 1 : 0;
+    });
+    bs->k10.resize(n);
     uint64_t dev_bytes = 0;
     size_t k = 0;
-    for (size_t i = 0; i < n; i++) {
-        bs->offsets[i] = bs->bytes.size();
+    assemble_bodies(bs, n, [&](size_t i) {
         bs->k10[i] = (int32_t)to[i].status;
-        if (to[i].status == GPUDIFF_TOK_OK) {
-            const uint8_t* p = raw.data() + to[i].off;
-            bs->bytes.insert(bs->bytes.end(), p, p + to[i].bytes);
-            dev_bytes += to[i].bytes;
-        } else {
-            bs->source[i] = GPUDIFF_BODY_HOST;
-            if (hok[k]) bs->bytes.insert(bs->bytes.end(), hb[k].begin(), hb[k].end());
-            else bs->status[i] = GPUDIFF_E_DECODE;
-            k++;
+        if (to[i].status != GPUDIFF_TOK_OK) {
+            const size_t h = k++;
+            return host_body_of(hb[h], hok[h]);
         }
-    }
-    bs->offsets[n] = bs->bytes.size();
+        dev_bytes += to[i].bytes;
+        return Body{Body::kDevice, raw.data() + to[i].off, to[i].bytes};
+    });
     wb->body_bytes = dev_bytes;
-    publish(bs, out, n, n_host);
+    publish(bs, out, n, def.size());
     return GPUDIFF_OK;
 }
 
@@ -525,17 +474,14 @@ int gpudiff_wbatch_stats_get(const gpudiff_wbatch* wb, gpudiff_wbatch_stats* st)
     st->scratch_bytes = wb->scratch_bytes;
     st->out_cap_bytes = wb->out_bytes;
     st->runs = wb->runs;
-    st->k10_ms = wb->runs ? wb->k10_ms_sum / (double)wb->runs : 0.0;
+    st->k10_ms = wb->mean_ms(0);
     return GPUDIFF_OK;
 }
 
 void gpudiff_wbatch_free(gpudiff_ctx* c, gpudiff_wbatch* wb) {
     if (!wb) return;
-    if (c && c->has_device) {
-        (void)hipSetDevice(c->device);
-        (void)hipStreamSynchronize(c->stream);
-    }
-    free_wbatch(wb);
+    doc_batch_quiesce(c);
+    delete wb;
 }
 
 int gpudiff_upsert_bodies(gpudiff_ctx* c, const uint8_t* const* docs, const size_t* lens, size_t n, uint32_t mode,
@@ -691,43 +637,24 @@ int gpudiff_write_plan_get_ex(gpudiff_ctx* c, gpudiff_ticket ticket, uint32_t mo
     std::vector<std::string> hb(def.size());
     std::vector<uint8_t> hok(def.size(), 0);
     const uint32_t mode_split = n_spec_docs;
-    {
-        const uint32_t T = std::max<uint32_t>(1, std::min<uint32_t>(c->threads, (uint32_t)((def.size() + 63) / 64)));
-        auto work = [&](uint32_t t) {
-            for (size_t k = t; k < def.size(); k += T) {
-                const TokDoc& d = docs[def[k]];
-                hok[k] = host_body(hjson.data() + hoff[k], d.json_len,
-                                   def[k] < mode_split ? GPUDIFF_UPSERT_SPEC : GPUDIFF_UPSERT_STATUS, hb[k])
-                             ? 1
-                             : 0;
-            }
-        };
-        workers(c).run(T, work);
-    }
+    for_deferred(c, def.size(), [&](size_t k) {
+        hok[k] = host_body(hjson.data() + hoff[k], docs[def[k]].json_len,
+                           def[k] < mode_split ? GPUDIFF_UPSERT_SPEC : GPUDIFF_UPSERT_STATUS, hb[k])
+                     ? 1
+                     : 0;
+    });
     std::vector<int32_t> hidx(nd, -1);
     for (size_t k = 0; k < def.size(); k++) hidx[def[k]] = (int32_t)k;
     BodiesStore* bs = new (std::nothrow) BodiesStore();
     if (!bs) return GPUDIFF_E_NOMEM;
-    bs->offsets.resize(nw + 1);
-    bs->status.assign(nw, 0);
     bs->k10.assign(nw, GPUDIFF_TOK_OK);
-    bs->source.assign(nw, GPUDIFF_BODY_DEVICE);
-    for (size_t w = 0; w < nw; w++) {
-        bs->offsets[w] = bs->bytes.size();
-        if (wdoc[w] == UINT32_MAX) continue;  // no-op write: no body
+    assemble_bodies(bs, nw, [&](size_t w) {
+        if (wdoc[w] == UINT32_MAX) return Body{Body::kNone, nullptr, 0};  // no-op write: no body
         const uint32_t k = wdoc[w];
         bs->k10[w] = (int32_t)to[k].status;
-        if (to[k].status == GPUDIFF_TOK_OK) {
-            const uint8_t* p = raw.data() + to[k].off;
-            bs->bytes.insert(bs->bytes.end(), p, p + to[k].bytes);
-        } else {
-            bs->source[w] = GPUDIFF_BODY_HOST;
-            const int32_t h = hidx[k];
-            if (hok[h]) bs->bytes.insert(bs->bytes.end(), hb[h].begin(), hb[h].end());
-            else bs->status[w] = GPUDIFF_E_DECODE;
-        }
-    }
-    bs->offsets[nw] = bs->bytes.size();
+        if (to[k].status != GPUDIFF_TOK_OK) return host_body_of(hb[hidx[k]], hok[hidx[k]]);
+        return Body{Body::kDevice, raw.data() + to[k].off, to[k].bytes};
+    });
     publish(bs, &out->bodies, nw, def.size());
     out->n = nw;
     out->pair_index = ps->pair_index.data();
@@ -755,41 +682,30 @@ int gpudiff_store_write_plan_get(gpudiff_ctx* c, gpudiff_store* st, gpudiff_tick
     const size_t nw = sp.n, n_def = sp.def.size();
     std::vector<std::string> hb(n_def);
     std::vector<uint8_t> hok(n_def, 0);
-    if (n_def) {
-        const uint32_t T = std::max<uint32_t>(1, std::min<uint32_t>(c->threads, (uint32_t)((n_def + 63) / 64)));
-        auto work = [&](uint32_t t) {
-            for (size_t k = t; k < n_def; k += T)
-                hok[k] = host_body(sp.hjson.data() + sp.hoff[k], sp.hlen[k], sp.kind[sp.def[k]], hb[k]) ? 1 : 0;
-        };
-        workers(c).run(T, work);
-    }
+    for_deferred(c, n_def, [&](size_t k) {
+        hok[k] = host_body(sp.hjson.data() + sp.hoff[k], sp.hlen[k], sp.kind[sp.def[k]], hb[k]) ? 1 : 0;
+    });
     std::unique_ptr<PlanStore> ps(new (std::nothrow) PlanStore());
     std::unique_ptr<BodiesStore> bs(new (std::nothrow) BodiesStore());
     if (!ps || !bs) return GPUDIFF_E_NOMEM;
     ps->pair_index.assign(sp.pair_index, sp.pair_index + nw);
     ps->kind.assign(sp.kind, sp.kind + nw);
     ps->noop.assign(sp.noop, sp.noop + nw);
-    bs->status.assign(nw, 0);
     bs->k10.assign(sp.k10, sp.k10 + nw);
-    bs->source.assign(nw, GPUDIFF_BODY_DEVICE);
     if (!n_def) {  // the device's dense bodies are the result as they are
+        bs->status.assign(nw, 0);
+        bs->source.assign(nw, GPUDIFF_BODY_DEVICE);
         bs->offsets.assign(sp.offsets, sp.offsets + nw + 1);
         bs->bytes.assign(sp.bytes, sp.bytes + sp.offsets[nw]);
     } else {  // the host's bodies go in between
-        bs->offsets.resize(nw + 1);
         size_t k = 0;
-        for (size_t w = 0; w < nw; w++) {
-            bs->offsets[w] = bs->bytes.size();
+        assemble_bodies(bs.get(), nw, [&](size_t w) {
             if (k < n_def && sp.def[k] == w) {
-                bs->source[w] = GPUDIFF_BODY_HOST;
-                if (hok[k]) bs->bytes.insert(bs->bytes.end(), hb[k].begin(), hb[k].end());
-                else bs->status[w] = GPUDIFF_E_DECODE;
-                k++;
-            } else {
-                bs->bytes.insert(bs->bytes.end(), sp.bytes + sp.offsets[w], sp.bytes + sp.offsets[w + 1]);
+                const size_t h = k++;
+                return host_body_of(hb[h], hok[h]);
             }
-        }
-        bs->offsets[nw] = bs->bytes.size();
+            return Body{Body::kDevice, sp.bytes + sp.offsets[w], (size_t)(sp.offsets[w + 1] - sp.offsets[w])};
+        });
     }
     publish(bs.release(), &out->bodies, nw, n_def);
     out->n = nw;

@@ -73,6 +73,36 @@ def test_empty_and_repeated_runs():
     eng.close()
 
 
+def test_doc_batch_every_branch():
+    """New sides [ordinary, empty, oversize, ordinary that defers, ordinary], then a pair without an old object and
+    one whose old side is the oversize document: every branch of the batch's layout, upload and host completion.
+    Actions equal the oracle's (the oversize document's: the oracle's for the unpadded one), twice-run timing
+    folded into two runs, and a fetch without a run in between returns the same."""
+    from tests.doc_batch_cases import oversize
+    old = C.obj(rv="1", labels=C.L, conds=C.C)
+    esc = C.obj(rv="2", gen=2, labels=C.L, conds=C.C)[:-1] + b',"k\\u0065y":"v"}'  # an escaped key
+    big = C.obj(rv="3", labels=C.L, conds=[C.cond(s="False")])
+    plain = [(old, C.obj(rv="2", labels=C.L, ann=C.A, conds=C.C)), (old, b""), (old, big), (old, esc),
+             (old, C.obj(rv="1", labels=C.L, conds=C.C)), (None, C.obj(rv="5")), (big, old)]
+    pairs = [(oversize(a) if a is big else a, oversize(b) if b is big else b) for a, b in plain]
+    want = [N.classify(a, b) for a, b in plain]
+    assert want == [N.META_ONLY, N.DECODE, N.STATUS_ONLY, N.SPEC_CHANGED, N.IGNORE, N.CREATED, N.STATUS_ONLY]
+    eng = G.Engine(device=0, timing=True)
+    nb = eng.nbatch(pairs)
+    nb.run()
+    nb.run()
+    a = nb.fetch().tolist()
+    assert nb.stats().runs == 2
+    b = nb.fetch().tolist()
+    st = nb.stats()
+    nb.close()
+    assert a == want and b == want
+    # the pairs holding the empty, the oversize (twice) and the deferring document are the host's
+    assert st.runs == 2 and st.n_host == 4 and st.n_pairs == len(pairs)
+    assert eng.classify_updates(pairs).tolist() == want
+    eng.close()
+
+
 def test_many_members_and_conditions_defer():
     eng = G.Engine(device=0)
     base = C.obj(rv="1", labels={"k%d" % i: "v" for i in range(20)}, conds=[C.cond(t="T%d" % i) for i in range(10)])

@@ -97,6 +97,40 @@ def test_staged_runs_repeat():
     eng.close()
 
 
+def test_doc_batch_every_branch():
+    """[ordinary, empty, oversize, ordinary that defers, ordinary]: every branch of the batch's layout, upload and
+    host completion.  Groups and sums equal the oracle's (the oversize document's: the oracle's for the unpadded
+    one), twice-run timing folded into two runs, and a fetch without a run in between returns the same."""
+    from tests.doc_batch_cases import oversize
+    plain = [C.dep({C.O: "r", "a": "b"}, {"replicas": 3, "readyReplicas": 1}), b"",
+             C.dep({C.O: "r"}, {"replicas": 5, "updatedReplicas": 2}),
+             C.dep({C.O: "q"}, {"replicas": 7, "availableReplicas": 4}, extra=',"k\\u0065y":"v"'),  # an escaped key
+             C.dep({C.O: "q"}, {"replicas": 11, "unavailableReplicas": 6})]
+    docs = list(plain)
+    docs[2] = oversize(plain[2])
+    want = R.rollup(plain)
+    assert want["doc_group"] == [0, R.GROUP_DECODE, 0, 1, 1]
+    wg = [{"first_doc": g["first_doc"], "n_members": g["n_members"], "sums": g["sums"]} for g in want["groups"]]
+    eng = G.Engine(device=0, timing=True)
+    rb = eng.rbatch(docs)
+    rb.run()
+    rb.run()
+    a = rb.fetch()
+    assert rb.stats().runs == 2
+    b = rb.fetch()
+    assert rb.stats().runs == 2
+    rb.close()
+    for res in (a, b):
+        got = res.as_dict()
+        assert got["doc_group"] == want["doc_group"] and got["groups"] == wg
+        k11 = res.k11_status.tolist()
+        assert k11[0] == k11[4] == G.TOK_OK and k11[2] == G.TOK_SIZE and k11[1] != G.TOK_OK and k11[3] != G.TOK_OK
+        assert res.n_host == sum(k != G.TOK_OK for k in k11) == 3 and res.host_grouped
+    one = eng.rollup_status(docs).as_dict()
+    assert one["doc_group"] == want["doc_group"] and one["groups"] == wg
+    eng.close()
+
+
 def test_empty_and_single():
     eng = G.Engine(device=0)
     r = eng.rollup_status([])

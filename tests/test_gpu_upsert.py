@@ -11,6 +11,7 @@ import pytest
 from kcp_amd import gpudiff as G
 from oracle import upsert_oracle as U
 from tests import upsert_cases as UC
+from tests.doc_batch_cases import oversize
 from tests.test_gpu_tokenize import EDGE_DEFER, EDGE_OK
 
 pytestmark = pytest.mark.gpu
@@ -117,6 +118,63 @@ def test_staged_batch_reruns_identical():
     wb.close()
     assert a.bodies == b.bodies and a.n_host == 0
     assert st.runs == 4 and st.k10_ms > 0 and st.body_bytes == sum(len(x) for x in a.bodies)
+    eng.close()
+
+
+ORDINARY = [b'{"apiVersion":"v1","kind":"ConfigMap","metadata":{"name":"cm-%d","uid":"u-%d","resourceVersion":"%d",'
+            b'"labels":{"app":"a"}},"data":{"k":"v%d"}}' % (i, i, 40 + i, i) for i in range(4)]
+ESCAPED_KEY = ORDINARY[3][:-1] + b',"k\\u0065y":"v"}'  # a key that needs unescaping: the kernel defers, Go decodes
+
+
+@pytest.mark.parametrize("mode", [UC.SPEC, UC.STATUS])
+def test_doc_batch_every_branch(mode):
+    """[ordinary, empty, oversize, ordinary that defers, ordinary]: every branch of the batch's layout, upload and
+    host completion.  Bodies byte-exact to the oracle's (the oversize document's: the oracle's for the unpadded
+    one), twice-run timing folded into two runs, and a fetch without a run in between returns the same."""
+    plain = [ORDINARY[0], b"", ORDINARY[1], ESCAPED_KEY, ORDINARY[2]]
+    docs = list(plain)
+    docs[2] = oversize(plain[2])
+    want = [U.upsert_body(d, mode) for d in plain]
+    assert want[1] is None and all(w is not None for i, w in enumerate(want) if i != 1)
+    eng = G.Engine(device=0, timing=True)
+    wb = eng.wbatch(docs, mode)
+    wb.run()
+    wb.run()
+    a = wb.fetch()
+    assert wb.stats().runs == 2
+    b = wb.fetch()
+    assert wb.stats().runs == 2
+    wb.close()
+    for res in (a, b):
+        assert res.bodies == want
+        k10 = [int(k) for k in res.k10_status]
+        assert k10[0] == k10[4] == G.TOK_OK and k10[2] == G.TOK_SIZE and k10[1] != G.TOK_OK and k10[3] != G.TOK_OK
+        assert [int(s) for s in res.source] == [G.BODY_DEVICE if k == G.TOK_OK else G.BODY_HOST for k in k10]
+        assert res.n_host == sum(k != G.TOK_OK for k in k10) == 3
+    assert eng.upsert_bodies(docs, mode).bodies == want
+    eng.close()
+
+
+def test_empty_batch():
+    """n = 0 through the C ABI: create, run, fetch, statistics and free of a batch without documents."""
+    import ctypes as C
+    L = G.lib()
+    eng = G.Engine(device=0, timing=True)
+    ptrs, lens = (C.c_void_p * 1)(), (C.c_size_t * 1)()
+    h = C.c_void_p()
+    assert L.gpudiff_wbatch_create(eng.ctx, ptrs, lens, 0, UC.SPEC, C.byref(h)) == G.OK and h
+    b = G.Bodies()
+    for _ in range(2):
+        assert L.gpudiff_wbatch_run(eng.ctx, h) == G.OK
+    assert L.gpudiff_wbatch_fetch(eng.ctx, h, C.byref(b)) == G.OK
+    assert b.n == 0 and b.n_host == 0 and C.cast(b.offsets, C.POINTER(C.c_uint64))[0] == 0
+    L.gpudiff_bodies_release(eng.ctx, C.byref(b))
+    st = G.WBatchStats()
+    assert L.gpudiff_wbatch_stats_get(h, C.byref(st)) == G.OK
+    assert st.n_docs == 0 and st.json_bytes == 0 and st.body_bytes == 0 and st.runs == 2
+    L.gpudiff_wbatch_free(eng.ctx, h)
+    assert L.gpudiff_upsert_bodies(eng.ctx, ptrs, lens, 0, UC.SPEC, C.byref(b)) == G.OK and b.n == 0
+    L.gpudiff_bodies_release(eng.ctx, C.byref(b))
     eng.close()
 
 
