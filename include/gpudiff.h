@@ -461,6 +461,40 @@ typedef struct gpudiff_cluster_index_stats {
     uint64_t timed_calls;
 } gpudiff_cluster_index_stats;
 int gpudiff_cluster_index_stats_get(gpudiff_ctx* ctx, gpudiff_cluster_index_stats* out);
+/* The index of ANY waited ticket, under the batch's final flags -- the ones gpudiff_wait returned in pair_flags:
+ * the same function, the same gpudiff_cluster_index (released with gpudiff_cluster_index_release), also for the
+ * tickets gpudiff_cluster_index_get refuses: device-encoded gpudiff_submit batches and every gpudiff_store_submit
+ * ticket, whose deferred rows the host resolved.  Such a row found clean is not in the index (a cluster whose only
+ * dirty row it was is not listed); one found dirty in one kind is in that kind's slice only; a conservative exit or
+ * an undecodable pair stays dirty in both.  A ticket gpudiff_cluster_index_get serves gets an identical index.
+ * On the device: the final dirty set is a subset of the pass's dirty list, so with host-resolved rows K26 writes
+ * their final flags over a copy of the pass's, K27 counts the list's entries that are still dirty (held to
+ * gpudiff_wait's n_dirty) and K28 compacts the list when some are not; K23 - K25 then run as they do for
+ * gpudiff_cluster_index_get.  At most four host synchronisations a call, three without host-resolved rows, none
+ * when nothing is dirty.  Runs on the context stream.
+ * Valid after gpudiff_wait on the ticket has returned and until that batch is diffed or submitted again (a store
+ * ticket: until its ring slot's next gpudiff_store_submit, the write plan's window).  GPUDIFF_E_STATE: anything
+ * else; GPUDIFF_E_NODEVICE: a host-only context; GPUDIFF_E_CAPACITY: out of device memory; GPUDIFF_E_DEVICE also when
+ * the device's counts disagree with the final ones (never a silently wrong index). */
+int gpudiff_cluster_index_get_final(gpudiff_ctx* ctx, gpudiff_ticket ticket, gpudiff_cluster_index* out);
+/* what the context's gpudiff_cluster_index_get_final calls cost since gpudiff_open (gpudiff_cluster_index_stats is
+ * not moved by them); kernel_ms needs GPUDIFF_OPT_TIMING (HIP events around K26 + K27 + scan and around K28, added to
+ * the three spans of gpudiff_cluster_index_stats).  GPUDIFF_E_NODEVICE on a host-only context. */
+typedef struct gpudiff_cluster_index_final_stats {
+    uint64_t calls;            /* calls that returned an index */
+    uint64_t patched_calls;    /* of those: the batch had host-resolved rows */
+    uint64_t compacted_calls;  /* of those: some entry of the pass's dirty list was dropped and K28 ran */
+    uint64_t sorted_calls;     /* the radix sort ran */
+    uint64_t syncs;            /* host synchronisations: at most 4 a call, 3 without host-resolved rows */
+    uint64_t entries_in;       /* entries of the passes' dirty lists */
+    uint64_t entries_live;     /* of those: still dirty under the final flags, indexed */
+    uint64_t patch_rows;       /* host-resolved rows whose final flags were uploaded (or, all clean, just counted) */
+    uint64_t h2d_bytes;        /* those uploads */
+    uint64_t d2h_bytes;        /* the packed blocks copied back */
+    double kernel_ms;
+    uint64_t timed_calls;
+} gpudiff_cluster_index_final_stats;
+int gpudiff_cluster_index_final_stats_get(gpudiff_ctx* ctx, gpudiff_cluster_index_final_stats* out);
 
 /* ---- device-resident object store (watch replay) ----
  * The informer cache's "old" objects stay resident in HBM, one per caller

@@ -447,12 +447,30 @@ func (e *Engine) ClusterIndex(ticket C.gpudiff_ticket) (*ClusterIndex, error) {
 		return nil, err
 	}
 	defer C.gpudiff_cluster_index_release(e.ctx, &ci)
+	return copyClusterIndex(&ci), nil
+}
+
+func copyClusterIndex(ci *C.gpudiff_cluster_index) *ClusterIndex {
 	nc := int(ci.n_clusters)
 	return &ClusterIndex{
 		ClusterIDs: copyU32(ci.cluster_ids, nc), SpecOff: copyU32(ci.spec_off, nc+1),
 		StatusOff: copyU32(ci.status_off, nc+1), SpecIDs: copyU32(ci.spec_ids, int(ci.n_spec)),
 		StatusIDs: copyU32(ci.status_ids, int(ci.n_status)), SortedOnDevice: ci.sorted_on_device != 0,
-	}, nil
+	}
+}
+
+// ClusterIndexFinal is ClusterIndex for any waited ticket, under the flags gpudiff_wait returned: also the Batcher's
+// device-encoded batches and every store ticket, whose deferred rows the host resolved (gpudiff_cluster_index_get_final,
+// kernels K26 - K28 in front of K23 - K25).  Valid until the batch is submitted again.
+func (e *Engine) ClusterIndexFinal(ticket C.gpudiff_ticket) (*ClusterIndex, error) {
+	var ci C.gpudiff_cluster_index
+	e.mu.Lock()
+	defer e.mu.Unlock()
+	if err := errOf(C.gpudiff_cluster_index_get_final(e.ctx, ticket, &ci)); err != nil {
+		return nil, err
+	}
+	defer C.gpudiff_cluster_index_release(e.ctx, &ci)
+	return copyClusterIndex(&ci), nil
 }
 
 func (b *Batcher) bytesHint(n int) int { return int(b.avgBytes*float64(n)*1.25) + 4096 }

@@ -14,7 +14,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 
 SOURCES = ["kernels.hip", "tokenize.hip", "rollup.hip", "negotiate.hip", "dstore.hip", "paths.hip", "plan.hip",
-           "scan64.hip", "smallpass.hip", "values.hip", "fanout.hip", "api.cpp", "fanout.cpp", "store.cpp", "dstore.cpp",
+           "scan64.hip", "smallpass.hip", "values.hip", "fanout.hip", "fanout_live.hip", "api.cpp", "fanout.cpp", "store.cpp", "dstore.cpp",
            "devenc.cpp", "doc_batch.cpp", "upsert.cpp", "rollup.cpp", "negotiate.cpp", "encoder.cpp", "json.cpp",
            "buildid.cpp"]
 SYNTH_SOURCES = ["synth.cpp", "encoder.cpp", "json.cpp", "buildid.cpp"]

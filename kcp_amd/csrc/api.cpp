@@ -858,13 +858,15 @@ int gpudiff_wait(gpudiff_ctx* c, gpudiff_ticket ticket, gpudiff_result* res) {
     std::unique_ptr<ResultStore> rs(new (std::nothrow) ResultStore());
     if (!rs) return GPUDIFF_E_NOMEM;
     if ((rc = collect_results(c, d, *rs))) return rc;
+    const uint32_t n_dev_dirty = (uint32_t)rs->dirty.size();  // the device's list, before a finisher resolves rows
     auto fin = c->finishers.find(ticket);
     if (fin != c->finishers.end()) {
         auto fn = std::move(fin->second);
         c->finishers.erase(fin);
         if ((rc = fn(*rs))) return rc;
     }
-    d->waited = WaitedMark{ticket, (uint32_t)rs->spec.size(), (uint32_t)rs->status.size(), (uint32_t)rs->dirty.size()};
+    d->waited = WaitedMark{ticket, (uint32_t)rs->spec.size(), (uint32_t)rs->status.size(), (uint32_t)rs->dirty.size(),
+                           n_dev_dirty};
     res->n_pairs = rs->flags.size();
     res->pair_flags = rs->flags.data();
     res->n_spec_dirty = rs->spec.size();

@@ -922,6 +922,7 @@ DStore* dstore_create(gpudiff_ctx* c, uint32_t max_slots, uint64_t space_bytes, 
         (void)hipFree(R.d->pool);
         R.d->pool = nullptr;
         R.d->pool_borrowed = true;
+        R.d->host_resolves = true;
         if ((rc = dalloc(&R.dcnt, 1))) return fail(rc);
         if (hipEventCreateWithFlags(&R.staged, hipEventDisableTiming) != hipSuccess ||
             hipEventCreateWithFlags(&R.k0_done, hipEventDisableTiming) != hipSuccess)
@@ -1405,6 +1406,7 @@ int finish_batch(DStore* s, Ring& R, ResultStore& rs) {
     }
     // the strings before resolve(): its compaction may pack into the space this batch's superseded blobs are in
     int rc = (R.strs || R.vals) ? render_text(s, R, rs) : GPUDIFF_OK;
+    R.d->final_patch = nullptr;
     R.plan_patch.clear();
     if (!rc && ndef) rc = resolve(s, R, rs);
     if (!rc && R.strs) {
@@ -1421,6 +1423,7 @@ int finish_batch(DStore* s, Ring& R, ResultStore& rs) {
     if (!rc && s->pair_mode)  // kept for gpudiff_write_plan_get
         R.final_flags.assign(rs.flags.begin(), rs.flags.end());
     if (!rc) R.waited = true;  // the ring slot holds a waited batch until its next submit (the write plans' window)
+    if (!rc) R.d->final_patch = &R.plan_patch;  // and gpudiff_cluster_index_get_final's: the resolved rows' final flags
     // forgets older than every outstanding batch are settled
     for (auto it = s->forgotten.begin(); it != s->forgotten.end();)
         it = it->second < s->next_wait ? s->forgotten.erase(it) : std::next(it);
@@ -1444,6 +1447,7 @@ int dstore_submit(gpudiff_ctx* c, DStore* s, const gpudiff_event* ev, size_t n, 
     if ((rc = claim_ring_slot(s, dec, &Rp))) return rc;
     Ring& R = *Rp;
     R.waited = false;  // its tables are rewritten from here on: the previous batch's write plan is gone
+    R.d->final_patch = nullptr;
     Lap lap{timing, s->t_sub};
     lap(0);
     const uint32_t batch = ++s->batch_seq;

@@ -62,7 +62,13 @@ struct gpudiff_hbatch {
 struct WaitedMark {
     gpudiff_ticket ticket = 0;
     uint32_t n_spec = 0, n_status = 0, n_dirty = 0;
+    // gpudiff_cluster_index_get_final: the length of the device pass's own dirty list (dirty_idx / dirty_ids), read
+    // before the ticket's finisher ran; n_dirty above counts what is left after the host resolved the deferred rows
+    uint32_t n_dev_dirty = 0;
 };
+namespace gd {
+struct PlanPatch;  // plan.h
+}
 struct FanBuffers;
 void fan_buffers_release(FanBuffers* f);
 struct FanCtx;
@@ -137,7 +143,12 @@ struct gpudiff_dbatch {
     uint8_t* small_image = nullptr;
     bool small_pending = false;
     WaitedMark waited;          // set by gpudiff_wait alone; waited.ticket == ticket: the device arrays are final
-    FanBuffers* fan = nullptr;  // allocated by the batch's first gpudiff_cluster_index_get
+    FanBuffers* fan = nullptr;  // allocated by the batch's first gpudiff_cluster_index_get / _get_final
+    // a device-encode store's ring batch (store or pair mode): the host resolves its deferred rows.  final_patch is
+    // those rows' final flags of the waited batch (Ring::plan_patch), set by the batch's finisher and null again from
+    // the ring slot's next submit on -- gpudiff_cluster_index_get_final's window, as the write plan's
+    bool host_resolves = false;
+    const std::vector<gd::PlanPatch>* final_patch = nullptr;
 };
 
 struct DStore;

@@ -324,6 +324,17 @@ class ClusterIndexStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class ClusterIndexFinalStats(C.Structure):
+    """gpudiff_cluster_index_final_stats: what the context's cluster_index_final calls cost since open."""
+    _fields_ = [("calls", C.c_uint64), ("patched_calls", C.c_uint64), ("compacted_calls", C.c_uint64),
+                ("sorted_calls", C.c_uint64), ("syncs", C.c_uint64), ("entries_in", C.c_uint64),
+                ("entries_live", C.c_uint64), ("patch_rows", C.c_uint64), ("h2d_bytes", C.c_uint64),
+                ("d2h_bytes", C.c_uint64), ("kernel_ms", C.c_double), ("timed_calls", C.c_uint64)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class DeviceView(C.Structure):
     _fields_ = [("pair_flags", C.c_void_p), ("spec_dirty_ids", C.c_void_p), ("status_dirty_ids", C.c_void_p),
                 ("dirty_ids", C.c_void_p), ("counts", C.c_void_p)]
@@ -390,6 +401,8 @@ SIGNATURES = [
     ("gpudiff_cluster_index_host", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                              C.POINTER(ClusterIndexC)]),
     ("gpudiff_cluster_index_stats_get", C.c_int, [_P, C.POINTER(ClusterIndexStats)]),
+    ("gpudiff_cluster_index_get_final", C.c_int, [_P, C.c_uint64, C.POINTER(ClusterIndexC)]),
+    ("gpudiff_cluster_index_final_stats_get", C.c_int, [_P, C.POINTER(ClusterIndexFinalStats)]),
     ("gpudiff_store_create", C.c_int, [_P, C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(_P)]),
     ("gpudiff_store_create_ex", C.c_int, [_P, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(_P)]),
     ("gpudiff_store_submit", C.c_int, [_P, _P, C.POINTER(Event), C.c_size_t, C.POINTER(C.c_uint64)]),
@@ -1031,6 +1044,22 @@ class Engine:
         (kernel_ms with timing)."""
         st = ClusterIndexStats()
         _chk(_lib.gpudiff_cluster_index_stats_get(self.ctx, C.byref(st)), "gpudiff_cluster_index_stats_get")
+        return st
+
+    def cluster_index_final(self, ticket: int) -> ClusterIndex:
+        """gpudiff_cluster_index_get_final: the index of any waited ticket under the flags wait() returned -- also
+        device-encoded submits and store tickets, whose deferred rows the host resolved (kernels K26 - K28 in front of
+        K23 - K25).  A ticket cluster_index serves gets the same index."""
+        ci = ClusterIndexC()
+        _chk(_lib.gpudiff_cluster_index_get_final(self.ctx, ticket, C.byref(ci)), "gpudiff_cluster_index_get_final")
+        return _take_cluster_index(self.ctx, ci)
+
+    def cluster_index_final_stats(self) -> ClusterIndexFinalStats:
+        """gpudiff_cluster_index_final_stats_get: calls, patched / compacted / sorted calls, host synchronisations,
+        entries in and live, patch rows, bytes up and down (kernel_ms with timing)."""
+        st = ClusterIndexFinalStats()
+        _chk(_lib.gpudiff_cluster_index_final_stats_get(self.ctx, C.byref(st)),
+             "gpudiff_cluster_index_final_stats_get")
         return st
 
     def pass_stats(self) -> PassStats:
