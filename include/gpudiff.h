@@ -299,7 +299,9 @@ int gpudiff_hbatch_info_get(const gpudiff_hbatch* hb, gpudiff_hbatch_info* info)
  * fills *pool and *rows (row offsets relative to *pool) before appending.
  * The decision kernel trusts a row's structural fields as it always trusted the sizes: a row whose flags_b carries
  * GPUDIFF_OBJ_SPEC_KEYS_EQ (gpudiff_format.h) states that both sides' spec keys[] are equal, and the whole 128-byte
- * lines holding only those keys are then not read or compared.  A caller that cannot vouch for it leaves the bit 0. */
+ * lines holding only those keys are then not read or compared; with GPUDIFF_OBJ_SPEC_SHAPE_EQ beside it the row states
+ * the same of both sides' spec metas[], and the lines holding only keys and metas are not read.  A caller that cannot
+ * vouch for a bit leaves it 0. */
 int gpudiff_hbatch_create(gpudiff_ctx* ctx, uint64_t pool_bytes, size_t n_pairs, uint64_t total_leaves,
                           gpudiff_hbatch** out, uint8_t** pool, gpudiff_pair_row** rows);
 /* reuses a host batch (staging ring): waits for its last H2D copy, grows the
@@ -370,10 +372,13 @@ void gpudiff_dbatch_free(gpudiff_ctx* ctx, gpudiff_dbatch* db);
  * 4/3 of the optimum (Graham's bound) and within one cluster's weight of the mean. */
 int gpudiff_cluster_bytes(const gpudiff_pair_row* rows, size_t n, uint32_t n_clusters, uint64_t* out);
 int gpudiff_shard_lpt(const uint64_t* weights, uint32_t n_clusters, uint32_t world, int32_t* owner);
-/* *out = the sum of gpudiff_pair_stream_bytes (gpudiff_format.h) over the rows: what the decision kernel reads for them
- * from their descriptors -- the format's bytes less the 64-B rows and the key holes.  For measurements: the shard
- * weight stays gpudiff_cluster_bytes. */
+/* *out = the sum of gpudiff_pair_stream_bytes (gpudiff_format.h) over the rows with GPUDIFF_OBJ_SPEC_SHAPE_EQ masked:
+ * the format's bytes less the 64-B rows and the key holes alone -- DESIGN.md §6n's measure, what the decision kernel
+ * read before it honoured shape holes.  For measurements: the shard weight stays gpudiff_cluster_bytes. */
 int gpudiff_rows_stream_bytes(const gpudiff_pair_row* rows, size_t n, uint64_t* out);
+/* *out = the same sum with every bit honoured: what the decision kernel really reads for the rows from their
+ * descriptors, key and shape holes left out (16 B + 32 B per streamed chunk, a pair) */
+int gpudiff_rows_read_bytes(const gpudiff_pair_row* rows, size_t n, uint64_t* out);
 
 /* ---- diff (the hot path) ---- */
 /* enqueue K2..K6 on the context stream; returns immediately */

@@ -78,6 +78,13 @@
  * (gpudiff_keys_hole).  Additive: a producer that leaves it 0 (the object stores, an older encoder) gets the keys
  * streamed as before. */
 #define GPUDIFF_OBJ_SPEC_KEYS_EQ 0x8u
+/* flags_b only, and only beside GPUDIFF_OBJ_SPEC_KEYS_EQ: A's and B's spec metas[] (each leaf's type tag and byte
+ * length) are element for element equal as well, so the two spec regions have the same shape -- the same paths, types
+ * and lengths -- and spec_ar_a == spec_ar_b follows.  Stated by the same loop of PairEncoder::encode_flat, never on a
+ * decode-error row.  K2 then also leaves out the whole lines that hold only spec metas (gpudiff_shape_hole): of such a
+ * pair it compares every value and tail byte on every pass, and trusts the keys and metas inside whole lines as it
+ * trusts the sizes.  Additive like the bit above: the object stores, K0 and an older encoder leave it 0. */
+#define GPUDIFF_OBJ_SPEC_SHAPE_EQ 0x10u
 /* object store: the path table kept after a resident blob's segments (the
  * "trailer"), which makes the store's old-vs-new path check exact.  Its n
  * entries are the region leaves and all their ancestors except the root,
@@ -153,6 +160,17 @@ GPUDIFF_HD static inline void gpudiff_keys_hole(uint32_t l, uint32_t* hs, uint32
     *hs = hi > lo ? (uint32_t)(lo >> 4) : 0u;
     *hl = hi > lo ? (uint32_t)((hi - lo) >> 4) : 0u;
 }
+/* ---- shape holes: keys[] and metas[] together occupy bytes [8 L, 16 L); a row that carries GPUDIFF_OBJ_SPEC_SHAPE_EQ
+ * beside GPUDIFF_OBJ_SPEC_KEYS_EQ lets K2 skip the whole units inside that span.  Twice the key span with the same two
+ * partial units at its ends: L = 16 is the first with a hole (one line), L = 17..23 have none, L = 24..31 one line,
+ * L = 28 skips 128 B a side, L = 184 1408 B.  The hole ends at the arena's first byte when 16 L is a multiple of the
+ * unit.  Contains gpudiff_keys_hole(L) whenever that is not empty. */
+GPUDIFF_HD static inline void gpudiff_shape_hole(uint32_t l, uint32_t* hs, uint32_t* hl) {
+    const uint64_t u = GPUDIFF_KEYS_HOLE_UNIT;
+    const uint64_t lo = (8ull * l + (u - 1u)) / u * u, hi = 16ull * l / u * u;
+    *hs = hi > lo ? (uint32_t)(lo >> 4) : 0u;
+    *hl = hi > lo ? (uint32_t)((hi - lo) >> 4) : 0u;
+}
 /* streamed spec chunk k of a pair with the hole (hs, hl) is chunk k + (k >= hs ? hl : 0) of the segment */
 GPUDIFF_HD static inline uint32_t gpudiff_hole_chunk(uint32_t k, uint32_t hs, uint32_t hl) {
     return k + (k >= hs ? hl : 0u);
@@ -187,7 +205,11 @@ GPUDIFF_HD static inline uint64_t gpudiff_pair_compare_bytes(const gpudiff_pair_
  *   word 0, 1   off_a >> 7, off_b >> 7                  (blobs are GPUDIFF_BLOB_ALIGN aligned)
  *   bits  0-18  spec segment bytes of A, in 16-B units  (word 2 | word 3 << 32)
  *   bits 19-37  spec segment bytes of B, in 16-B units; under SPEC_EQ (B's equal A's) the skip L instead: the spec
- *               leaf count when the row carries GPUDIFF_OBJ_SPEC_KEYS_EQ, no error and a non-empty key hole, else 0
+ *               leaf count when the row carries GPUDIFF_OBJ_SPEC_KEYS_EQ, no error and a non-empty key hole, else 0.
+ *               A skip L never exceeds A's field (16 L <= the segment), so with A's field below GPUDIFF_PD_SHAPE_L
+ *               (a spec segment under 4 MiB) a value of GPUDIFF_PD_SHAPE_L or more is free: L | GPUDIFF_PD_SHAPE_L
+ *               says that the row carries GPUDIFF_OBJ_SPEC_SHAPE_EQ too and its shape hole is not empty.  A shape
+ *               row of 4 MiB or more keeps the key hole's code (no real object is that large).
  *   bits 38-56  status segment bytes of A, in 16-B units
  *   bits 57-63  GPUDIFF_PD_* >> 0
  *
@@ -207,6 +229,7 @@ GPUDIFF_HD static inline uint64_t gpudiff_pair_compare_bytes(const gpudiff_pair_
 #define GPUDIFF_PD_SIZE_BITS 19u
 #define GPUDIFF_PD_SIZE_MAX 0x7FFFFu  /* 16-B units: segments below 8 MiB */
 #define GPUDIFF_PD_ESCAPE 0xFFFFFFFFu
+#define GPUDIFF_PD_SHAPE_L 0x40000u   /* in the skip L field: the hole is the shape hole, L the low 18 bits */
 
 typedef struct gpudiff_pair_desc {
     uint32_t w[4];
@@ -218,15 +241,16 @@ typedef struct gpudiff_pair_geom {
     uint64_t off_a, off_b;
     uint32_t n1, n2, adj_a, adj_b;
     uint32_t bits;
-    uint32_t hs, hl; /* the key hole left out of the n1 spec chunks (16-B chunks; hl 0: none) */
+    uint32_t hs, hl; /* the key or shape hole left out of the n1 spec chunks (16-B chunks; hl 0: none) */
 } gpudiff_pair_geom;
 
 /* the stream's chunk counts from the segment bytes and the bits: K2's rule (gpudiff_pair_compare_bytes counts the
  * same chunks, the hole included).  skip_l: the spec leaf count of a pair whose spec keys need no compare, else 0;
- * a count whose keys would not lie inside the streamed spec span (never a packer's) is taken as 0 */
+ * shape: its metas need none either (the hole is gpudiff_shape_hole).  A count whose keys (and metas) would not lie
+ * inside the streamed spec span (never a packer's) is taken as 0 */
 GPUDIFF_HD static inline gpudiff_pair_geom gpudiff_pair_geom_of(uint64_t off_a, uint64_t off_b, uint32_t seg_a,
                                                                 uint32_t seg_b, uint32_t seg_t, uint32_t bits,
-                                                                uint32_t skip_l) {
+                                                                uint32_t skip_l, int shape) {
     gpudiff_pair_geom g;
     const int ok = !(bits & GPUDIFF_PD_ERR);
     const int spec_sz = (bits & GPUDIFF_PD_SPEC_EQ) != 0u;
@@ -237,8 +261,9 @@ GPUDIFF_HD static inline gpudiff_pair_geom gpudiff_pair_geom_of(uint64_t off_a, 
     g.n1 = (ok && spec_sz) ? ((!stat_sz && (bits & GPUDIFF_PD_NO_STAT)) ? ((seg_a + 127u) & ~127u) : seg_a) >> 4 : 0u;
     g.n2 = (ok && stat_sz) ? (spec_sz ? r128 - seg_a : seg_t) >> 4 : 0u;
     g.hs = g.hl = 0u;
-    if (skip_l && (uint64_t)skip_l * 12u <= 16ull * g.n1) {
-        gpudiff_keys_hole(skip_l, &g.hs, &g.hl);
+    if (skip_l && (uint64_t)skip_l * (shape ? 16u : 12u) <= 16ull * g.n1) {
+        if (shape) gpudiff_shape_hole(skip_l, &g.hs, &g.hl);
+        else gpudiff_keys_hole(skip_l, &g.hs, &g.hl);
         g.n1 -= g.hl;
     }
     g.adj_a = seg_a - 16u * g.n1;
@@ -261,7 +286,7 @@ GPUDIFF_HD static inline uint32_t gpudiff_pair_row_bits(const gpudiff_pair_row* 
 GPUDIFF_HD static inline gpudiff_pair_geom gpudiff_pair_row_geom(const gpudiff_pair_row* r) {
     return gpudiff_pair_geom_of(r->off_a, r->off_b, (uint32_t)gpudiff_seg_bytes(r->spec_l_a, r->spec_ar_a),
                                 (uint32_t)gpudiff_seg_bytes(r->spec_l_b, r->spec_ar_b),
-                                (uint32_t)gpudiff_seg_bytes(r->stat_l_a, r->stat_ar_a), gpudiff_pair_row_bits(r), 0u);
+                                (uint32_t)gpudiff_seg_bytes(r->stat_l_a, r->stat_ar_a), gpudiff_pair_row_bits(r), 0u, 0);
 }
 
 GPUDIFF_HD static inline gpudiff_pair_desc gpudiff_pair_desc_pack(const gpudiff_pair_row* r) {
@@ -284,8 +309,16 @@ GPUDIFF_HD static inline gpudiff_pair_desc gpudiff_pair_desc_pack(const gpudiff_
         uint64_t f1 = sb >> 4;
         if (bits & GPUDIFF_PD_SPEC_EQ) {
             uint32_t hs = 0, hl = 0;
-            if ((r->flags_b & GPUDIFF_OBJ_SPEC_KEYS_EQ) && !(bits & GPUDIFF_PD_ERR)) gpudiff_keys_hole(r->spec_l_a, &hs, &hl);
-            f1 = hl ? r->spec_l_a : 0u;
+            const int keys = (r->flags_b & GPUDIFF_OBJ_SPEC_KEYS_EQ) && !(bits & GPUDIFF_PD_ERR);
+            f1 = 0u;
+            if (keys && (r->flags_b & GPUDIFF_OBJ_SPEC_SHAPE_EQ) && (sa >> 4) < GPUDIFF_PD_SHAPE_L) {
+                gpudiff_shape_hole(r->spec_l_a, &hs, &hl);
+                if (hl) f1 = r->spec_l_a | GPUDIFF_PD_SHAPE_L;
+            }
+            if (keys && !f1) { /* (an empty shape hole: the key hole inside it is empty too) */
+                gpudiff_keys_hole(r->spec_l_a, &hs, &hl);
+                f1 = hl ? r->spec_l_a : 0u;
+            }
         }
         const uint64_t zw = (sa >> 4) | (f1 << GPUDIFF_PD_SIZE_BITS) | ((st >> 4) << (2u * GPUDIFF_PD_SIZE_BITS)) |
                             ((uint64_t)bits << (3u * GPUDIFF_PD_SIZE_BITS));
@@ -306,13 +339,16 @@ GPUDIFF_HD static inline gpudiff_pair_geom gpudiff_pair_desc_unpack(uint32_t w0,
     const uint32_t seg_a = (w2 & GPUDIFF_PD_SIZE_MAX) << 4;
     const uint32_t f1 = (uint32_t)(zw >> GPUDIFF_PD_SIZE_BITS) & GPUDIFF_PD_SIZE_MAX;
     const int eq = (bits & GPUDIFF_PD_SPEC_EQ) != 0u;
+    /* L <= A's field: below GPUDIFF_PD_SHAPE_L there, a skip field at or above it is L | GPUDIFF_PD_SHAPE_L */
+    const int shape = eq && f1 >= GPUDIFF_PD_SHAPE_L && (w2 & GPUDIFF_PD_SIZE_MAX) < GPUDIFF_PD_SHAPE_L;
     return gpudiff_pair_geom_of((uint64_t)w0 << 7, (uint64_t)w1 << 7, seg_a, eq ? seg_a : f1 << 4,
                                 ((w3 >> (2u * GPUDIFF_PD_SIZE_BITS - 32u)) & GPUDIFF_PD_SIZE_MAX) << 4, bits,
-                                eq ? f1 : 0u);
+                                eq ? (shape ? f1 & (GPUDIFF_PD_SHAPE_L - 1u) : f1) : 0u, shape);
 }
 
-/* the bytes the descriptor kernel reads for one pair: its 16-B descriptor and both sides' streamed chunks, key holes
- * left out (an escape's pair streams from its row: no hole).  gpudiff_pair_compare_bytes stays the format's bytes. */
+/* the bytes the descriptor kernel reads for one pair: its 16-B descriptor and both sides' streamed chunks, key and
+ * shape holes left out (an escape's pair streams from its row: no hole).  gpudiff_pair_compare_bytes stays the
+ * format's bytes. */
 GPUDIFF_HD static inline uint64_t gpudiff_pair_stream_bytes(const gpudiff_pair_row* r) {
     const gpudiff_pair_desc d = gpudiff_pair_desc_pack(r);
     const gpudiff_pair_geom g = gpudiff_pair_desc_is_escape(d.w[3]) ? gpudiff_pair_row_geom(r)

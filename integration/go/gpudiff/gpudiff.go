@@ -1026,6 +1026,26 @@ const OptDeviceEncode = uint32(C.GPUDIFF_OPT_DEVICE_ENCODE)
 // one read-back; results are the ordinary pass's.  A Batcher with a short flush window wants it.
 const OptSmallPass = uint32(C.GPUDIFF_OPT_SMALL_PASS)
 
+// Structural facts a producer of pre-encoded pair rows may state in a row's flags_b (gpudiff_format.h); the host
+// encoder states both.  ObjSpecKeysEq: both sides' spec keys[] are element for element equal.  ObjSpecShapeEq, only
+// beside it: the spec metas[] (every leaf's type tag and byte length) are equal too.  K2 leaves the whole 128-byte
+// lines that hold only those arrays out of its stream, so a caller that cannot vouch for a bit leaves it 0.
+const (
+	ObjSpecKeysEq  = uint32(C.GPUDIFF_OBJ_SPEC_KEYS_EQ)
+	ObjSpecShapeEq = uint32(C.GPUDIFF_OBJ_SPEC_SHAPE_EQ)
+)
+
+// RowsReadBytes sums what the decision kernel reads for n pair rows (gpudiff_pair_row, 64 bytes each) from their
+// descriptors, key and shape holes left out (gpudiff_rows_read_bytes).  For measurements; the shard weight stays the
+// format's bytes.
+func RowsReadBytes(rows unsafe.Pointer, n int) (uint64, error) {
+	var out C.uint64_t
+	if err := errOf(C.gpudiff_rows_read_bytes((*C.gpudiff_pair_row)(rows), C.size_t(n), &out)); err != nil {
+		return 0, err
+	}
+	return uint64(out), nil
+}
+
 // Write is one API call the syncer's decisions imply (gpudiff_write_plan_get_ex).  For informer
 // pairs (PlanInformer) both kinds render the NEW object -- UpdateFunc enqueues newObj
 // (specsyncer.go:47-50, statussyncer.go:32-35) and the worker writes it: a spec write is

@@ -613,6 +613,18 @@ int gpudiff_cluster_bytes(const gpudiff_pair_row* rows, size_t n, uint32_t n_clu
 int gpudiff_rows_stream_bytes(const gpudiff_pair_row* rows, size_t n, uint64_t* out) {
     if ((n && !rows) || !out) return GPUDIFF_E_INVAL;
     uint64_t sum = 0;
+    for (size_t i = 0; i < n; i++) {  // the key holes alone: a row's GPUDIFF_OBJ_SPEC_SHAPE_EQ is not honoured here
+        gpudiff_pair_row r = rows[i];
+        r.flags_b &= ~GPUDIFF_OBJ_SPEC_SHAPE_EQ;
+        sum += gpudiff_pair_stream_bytes(&r);
+    }
+    *out = sum;
+    return GPUDIFF_OK;
+}
+
+int gpudiff_rows_read_bytes(const gpudiff_pair_row* rows, size_t n, uint64_t* out) {
+    if ((n && !rows) || !out) return GPUDIFF_E_INVAL;
+    uint64_t sum = 0;
     for (size_t i = 0; i < n; i++) sum += gpudiff_pair_stream_bytes(&rows[i]);
     *out = sum;
     return GPUDIFF_OK;

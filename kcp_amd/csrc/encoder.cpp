@@ -295,6 +295,10 @@ void PairEncoder::encode_flat(FlatObject* fa, FlatObject* fb, uint32_t pair_id, 
     bool keys_eq = fa->spec.size() == fb->spec.size();
     for (size_t i = 0; keys_eq && i < fa->spec.size(); i++) keys_eq = (uint32_t)fa->spec[i].h == (uint32_t)fb->spec[i].h;
     if (keys_eq) row.flags_b |= GPUDIFF_OBJ_SPEC_KEYS_EQ;
+    // ... and, leaf i beside leaf i, whether the metas[] just written are equal too: every path's type and length
+    bool shape_eq = keys_eq;
+    for (size_t i = 0; shape_eq && i < fa->spec.size(); i++) shape_eq = fa->spec[i].meta == fb->spec[i].meta;
+    if (shape_eq) row.flags_b |= GPUDIFF_OBJ_SPEC_SHAPE_EQ;
 }
 
 void PairEncoder::encode_nodes(const Node* a, const Node* b, uint32_t pair_id, uint32_t cluster_id,

@@ -151,7 +151,7 @@ struct StreamLog {
     uint32_t cnt[2][64];             // [status][pair]
     uint32_t ent[2][64][kSpLogCap];  // sp_entry(the chunk's index in the item's stream, its differing dwords)
     uint32_t first[64], n1[64];      // a pair's first chunk in the item's stream, its streamed spec chunks
-    uint32_t hole[64];               // its key hole (sp_hole_word): a logged spec chunk's place in the segment
+    uint32_t hole[64];               // its key or shape hole (sp_hole_word): a logged spec chunk's place in the segment
 };
 
 // The changed paths of a size-matched region from its c <= kSpLogCap logged chunks, by stream_paths.h's rule (a
@@ -752,7 +752,7 @@ __global__ __launch_bounds__(256, MINB) void k_compare_flat(const gpudiff_pair_r
         slog = &stream_logs[uni(threadIdx.x >> 6)];
     }
     // one pass of a wave over chunks [base, base + 64 U) of an item's flattened stream (lane k's registers: pair k's
-    // inclusive chunk prefix, first chunk, spec chunks, arena adjustments and blob offsets; DESC: its key hole as
+    // inclusive chunk prefix, first chunk, spec chunks, arena adjustments and blob offsets; DESC: its key or shape hole as
     // sp_hole_word, which the spec chunks from the hole's start on step over); mismatching chunks mark their pairs in
     // mis_s / mis_t
     auto stream_pass = [&](uint32_t base, uint32_t total, uint32_t incl, uint32_t first, uint32_t n1, uint32_t adj_a,
@@ -922,7 +922,7 @@ __global__ __launch_bounds__(256, MINB) void k_compare_flat(const gpudiff_pair_r
         uint64_t off_a, off_b;
         bool err, spec_sz, has_st_b, stat_sz;
         uint32_t n1, n2, adj_a, adj_b;
-        [[maybe_unused]] uint32_t hole = 0;  // DESC: the pair's key hole (sp_hole_word)
+        [[maybe_unused]] uint32_t hole = 0;  // DESC: the pair's key or shape hole (sp_hole_word)
         // DESC: the pair's GPUDIFF_PD_* bits | kPdRow (its descriptor is the escape): all the stream leaves alive
         [[maybe_unused]] uint32_t dbits = 0;
         constexpr uint32_t kPdRow = 0x80u;
@@ -945,7 +945,8 @@ __global__ __launch_bounds__(256, MINB) void k_compare_flat(const gpudiff_pair_r
             // B's status chunk k lies at off_b + 16 k + adj_b.  A pair has spec chunks only with equal spec sizes, and then
             // adj_b == adj_a; without them every chunk takes the adjustment.  So adj_b - adj_a (= seg_b - seg_a) goes
             // into off_b once and the stream adds adj_a on both sides: the lane register and the cross-lane read per
-            // chunk this frees carry the key hole instead
+            // chunk this frees carry the hole instead (the keys' lines, or the keys' and metas' when the row says so:
+            // which of the two is settled here, by the unpack, before the stream)
             off_b += (uint64_t)g.adj_b - (uint64_t)g.adj_a;  // (each zero-extended, as the stream adds adj_a)
             adj_a = adj_b = g.adj_a;
             hole = sp_hole_word(g.hs, g.hl);

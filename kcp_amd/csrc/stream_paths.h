@@ -37,10 +37,14 @@ GD_SP_HD inline uint32_t sp_entry(uint32_t chunk, uint32_t dwords) { return (chu
 GD_SP_HD inline uint32_t sp_entry_dwords(uint32_t e) { return e & 15u; }
 GD_SP_HD inline uint64_t sp_entry_byte(uint32_t e, uint32_t d) { return 16ull * (e >> 4) + 4u * d; }
 
-// A pair's key hole (gpudiff_keys_hole: hs, hl in 16-B chunks, both multiples of 8 -- whole lines) as the one word K2
+// A pair's key or shape hole (gpudiff_keys_hole, gpudiff_shape_hole: hs, hl in 16-B chunks, both multiples of 8 -- whole
+// lines; a descriptor's L is below 2^19, so both halves fit) as the one word K2
 // keeps per lane and per pair of the log: hs / 8 | hl / 8 << 16; 0: no hole.  Streamed spec chunk k of the pair is
 // chunk k + (k >= hs ? hl : 0) of the segment (gpudiff_hole_chunk): the stream adds sp_hole_bytes to the address, and a
-// logged entry goes back through sp_entry_unhole before sp_entry_byte, so the rule above sees segment bytes.
+// logged entry goes back through sp_entry_unhole before sp_entry_byte, so the rule above sees segment bytes.  A shape
+// hole may end at the arena's first byte (16 L a multiple of 128) or at the streamed span's end (no arena, no status):
+// the chunk behind it is then an arena chunk, or there is none.  The rule reads the metas it needs (the owners of arena
+// dwords, the padded tail lengths of S) from memory, never from the stream: the metas inside a hole are the equal ones.
 static_assert(GPUDIFF_KEYS_HOLE_UNIT % 128u == 0u, "sp_hole_word keeps the hole in 128-B lines");
 GD_SP_HD inline uint32_t sp_hole_word(uint32_t hs, uint32_t hl) { return (hs >> 3) | ((hl >> 3) << 16); }
 GD_SP_HD inline uint32_t sp_hole_start(uint32_t w) { return (w & 0xFFFFu) << 3; }   // chunks; only read when hl != 0

@@ -45,6 +45,7 @@ DEVICE_CURRENT, DEVICE_NONE = -1, -2
 PATH_HASH_BITS = 32  # GPUDIFF_PATH_HASH_BITS: segment keys and reported path hashes
 OBJ_HAS_STATUS, OBJ_DECODE_ERR, OBJ_FRESH, OBJ_SEED_SHIFT = 0x1, 0x2, 0x4, 8
 OBJ_SPEC_KEYS_EQ = 0x8  # flags_b only: both sides' spec keys[] are equal (the host encoder; K2 skips the lines of keys)
+OBJ_SPEC_SHAPE_EQ = 0x10  # flags_b only, beside OBJ_SPEC_KEYS_EQ: the spec metas[] are equal too (K2 skips their lines)
 STORE_DEVICE_ENCODE = 0x1
 EXPORT_COUNTS, EXPORT_SPEC_IDS, EXPORT_STATUS_IDS, EXPORT_DIRTY_IDS, EXPORT_FLAGS = range(5)
 
@@ -377,6 +378,7 @@ SIGNATURES = [
     ("gpudiff_cluster_bytes", C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
     ("gpudiff_shard_lpt", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     ("gpudiff_rows_stream_bytes", C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]),
+    ("gpudiff_rows_read_bytes", C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]),
     ("gpudiff_diff", C.c_int, [_P, _P, C.POINTER(C.c_uint64)]),
     ("gpudiff_wait", C.c_int, [_P, C.c_uint64, C.POINTER(Result)]),
     ("gpudiff_result_release", None, [_P, C.POINTER(Result)]),
@@ -535,10 +537,20 @@ def cluster_bytes(rows: np.ndarray, n_clusters: int) -> np.ndarray:
 
 
 def stream_bytes(rows: np.ndarray) -> int:
-    """What K2 reads for these rows from their 16-B descriptors, key holes left out (gpudiff_rows_stream_bytes)."""
+    """What K2 would read for these rows from their 16-B descriptors with the key holes alone left out: DESIGN.md
+    §6n's measure, OBJ_SPEC_SHAPE_EQ not honoured (gpudiff_rows_stream_bytes)."""
     rows = np.ascontiguousarray(rows, dtype=ROW_DTYPE)
     out = C.c_uint64()
     _chk(_lib.gpudiff_rows_stream_bytes(rows.ctypes.data, rows.size, C.byref(out)), "gpudiff_rows_stream_bytes")
+    return int(out.value)
+
+
+def read_bytes(rows: np.ndarray) -> int:
+    """What K2 really reads for these rows from their 16-B descriptors, key and shape holes left out
+    (gpudiff_rows_read_bytes)."""
+    rows = np.ascontiguousarray(rows, dtype=ROW_DTYPE)
+    out = C.c_uint64()
+    _chk(_lib.gpudiff_rows_read_bytes(rows.ctypes.data, rows.size, C.byref(out)), "gpudiff_rows_read_bytes")
     return int(out.value)
 
 

@@ -1,6 +1,7 @@
-"""The bytes K2's descriptor stream reads for the first pairs of a synthetic population, and the share its key holes
-leave out (gpudiff_pair_stream_bytes, include/gpudiff_format.h), summed on the host from the product encoder's rows.
-No GPU needed.
+"""The bytes K2's descriptor stream reads for the first pairs of a synthetic population, and the share its key and
+shape holes leave out (gpudiff_pair_stream_bytes, include/gpudiff_format.h), summed on the host from the product
+encoder's rows: both sums, with the key holes alone (gpudiff_rows_stream_bytes, DESIGN.md §6n's measure) and with the
+shape holes the kernel honours (gpudiff_rows_read_bytes).  No GPU needed.
 
     python tools/keys_hole_bytes.py --config config3 --population 200000 --pairs 100000
 """
@@ -27,8 +28,8 @@ def main():
     pop = S.Population(S.make_cfg(args.config, n_pairs=args.population, n_clusters=max(1, args.population // 100)))
     eng = G.Engine(device=G.DEVICE_NONE, encode_threads=args.threads)
     n = min(args.pairs, pop.n)
-    out = dict(config=args.config, pairs=n, format_bytes=0, stream_bytes=0, stream_bytes_no_holes=0, sizes_eq=0,
-               keys_eq=0, pairs_with_hole=0)
+    out = dict(config=args.config, pairs=n, format_bytes=0, stream_bytes=0, read_bytes=0, stream_bytes_no_holes=0,
+               sizes_eq=0, keys_eq=0, shape_eq=0, pairs_with_hole=0, pairs_with_shape_hole=0)
     pos = 0
     while pos < n:
         m = min(65536, n - pos)
@@ -37,22 +38,31 @@ def main():
         ok = ((rows["flags_a"] | rows["flags_b"]) & G.OBJ_DECODE_ERR) == 0
         eq = ok & (rows["spec_l_a"] == rows["spec_l_b"]) & (rows["spec_ar_a"] == rows["spec_ar_b"])
         bit = (rows["flags_b"] & G.OBJ_SPEC_KEYS_EQ) != 0
+        sbit = bit & ((rows["flags_b"] & G.OBJ_SPEC_SHAPE_EQ) != 0)
         L = rows["spec_l_a"].astype(np.int64)
         hole = (12 * L // 128 * 128) > ((8 * L + 127) // 128 * 128)
+        shole = (16 * L // 128 * 128) > ((8 * L + 127) // 128 * 128)
         out["format_bytes"] += int(G.cluster_bytes(rows, int(rows["cluster_id"].max()) + 1).sum())
         out["stream_bytes"] += G.stream_bytes(rows)
+        out["read_bytes"] += G.read_bytes(rows)
         plain = rows.copy()
         plain["flags_b"] &= ~np.uint32(G.OBJ_SPEC_KEYS_EQ)
         out["stream_bytes_no_holes"] += G.stream_bytes(plain)
         out["sizes_eq"] += int(eq.sum())
         out["keys_eq"] += int((eq & bit).sum())
+        out["shape_eq"] += int((eq & sbit).sum())
         out["pairs_with_hole"] += int((eq & bit & hole).sum())
+        out["pairs_with_shape_hole"] += int((eq & sbit & shole).sum())
         hb.free()
         pos += m
     out["hole_bytes"] = out["stream_bytes_no_holes"] - out["stream_bytes"]
     out["hole_bytes_per_pair"] = out["hole_bytes"] / n
     out["stream_bytes_per_pair_no_holes"] = out["stream_bytes_no_holes"] / n
     out["hole_share"] = out["hole_bytes"] / out["stream_bytes_no_holes"]
+    out["shape_hole_bytes"] = out["stream_bytes_no_holes"] - out["read_bytes"]
+    out["shape_hole_bytes_per_pair"] = out["shape_hole_bytes"] / n
+    out["shape_hole_share"] = out["shape_hole_bytes"] / out["stream_bytes_no_holes"]
+    out["read_over_stream"] = out["read_bytes"] / out["stream_bytes"]
     print(json.dumps(out))
     eng.close()
     pop.close()
