@@ -800,6 +800,62 @@ void gpudiff_wbatch_free(gpudiff_ctx* ctx, gpudiff_wbatch* wb);
 int gpudiff_upsert_body_host(const uint8_t* doc, size_t len, uint32_t mode, uint8_t* out, size_t cap,
                              size_t* out_len);
 
+/* ---- the Update body: where the live resourceVersion goes ----
+ * Every steady-state write sets the live object's resourceVersion on the body it sends: updateStatusInUpstream
+ * always (Get -> SetResourceVersion(existing.GetResourceVersion()) -> UpdateStatus, pkg/syncer/statussyncer.go:50-57),
+ * upsertIntoDownstream on every AlreadyExists (specsyncer.go:116-124).  SetResourceVersion(rv) with rv != "" is
+ * SetNestedField(obj, rv, "metadata", "resourceVersion"): the member is set when metadata is a map, a new map
+ * {"resourceVersion": rv} is created when the metadata key is absent, and nothing changes when metadata is present
+ * and not a map (the accessor drops SetNestedField's error); rv == "" removes the field, which the body above has
+ * done already.  The bytes stay json.NewEncoder(w).Encode(obj.Object): keys sorted, rv escaped as any Go string.
+ *
+ * With each body the engine reports where that member goes, so the Update body is two copies around a short string
+ * once the Get has returned -- no decode, no second marshal.  One descriptor per body: `off`, a byte offset from the
+ * body's first byte, and `form`:
+ *   GPUDIFF_RV_NONE    no splice: the Update body is the body (metadata present and not a map; a write without a
+ *                      body -- a no-op or a decode error)
+ *   GPUDIFF_RV_INSERT  insert the member text at off
+ *   GPUDIFF_RV_LEAD    the inserted text starts with ','
+ *   GPUDIFF_RV_TRAIL   the inserted text ends with ','
+ *   GPUDIFF_RV_WRAP    the member text is "metadata":{"resourceVersion":"<rv>"} instead of "resourceVersion":"<rv>"
+ *                      (no metadata key at the root)
+ * The choice is canonical, so that descriptors compare byte for byte: a visible member precedes in the container:
+ * LEAD, off just past that member's value (where its ',' or the closing '}' stands); none precedes and one follows:
+ * TRAIL, off just past the container's '{'; neither: no comma, off just past '{'.  Visible = emitted in the body
+ * (not uid, not an ownerReferences member the spec transform removed).  Kernel K10 computes the descriptor for the
+ * bodies it renders, the host path for the ones it marshals. */
+#define GPUDIFF_RV_NONE 0u
+#define GPUDIFF_RV_INSERT 0x1u
+#define GPUDIFF_RV_LEAD 0x2u
+#define GPUDIFF_RV_TRAIL 0x4u
+#define GPUDIFF_RV_WRAP 0x8u
+typedef struct gpudiff_rv_splice {
+    size_t n;             /* = the bodies' n */
+    const uint32_t* off;  /* n */
+    const uint8_t* form;  /* n: GPUDIFF_RV_* */
+    size_t n_device;      /* descriptors K10 computed (the bodies it rendered) */
+    size_t n_host;        /* descriptors the host path computed (the bodies it marshalled; not decode errors) */
+} gpudiff_rv_splice;
+/* The descriptors of `b` (of gpudiff_upsert_bodies / gpudiff_wbatch_fetch, or &plan.bodies of either write plan).
+ * The arrays live as long as the bodies do (gpudiff_bodies_release / gpudiff_write_plan_release). */
+int gpudiff_bodies_rv_splice(gpudiff_ctx* ctx, const gpudiff_bodies* b, gpudiff_rv_splice* out);
+/* body[0, len) with the resourceVersion member spliced in as (off, form) say, into out[0, cap); host only, no
+ * context.  rv is escaped as Go escapes any string (HTML-safe, each invalid UTF-8 byte written as the escape of U+FFFD).  rv_len == 0 or
+ * GPUDIFF_RV_NONE copies the body.  *out_len = the result's length, also when it does not fit (then
+ * GPUDIFF_E_CAPACITY).  GPUDIFF_E_INVAL: an unknown form bit, form bits without GPUDIFF_RV_INSERT, or an off that
+ * is not inside the body (0 < off < len when inserting). */
+int gpudiff_splice_resource_version(const uint8_t* body, size_t len, uint32_t off, uint32_t form, const uint8_t* rv,
+                                    size_t rv_len, uint8_t* out, size_t cap, size_t* out_len);
+/* gpudiff_upsert_body_host plus the body's descriptor (*off, *form), as the host path records it while it writes
+ * the body. */
+int gpudiff_upsert_body_host_rv(const uint8_t* doc, size_t len, uint32_t mode, uint8_t* out, size_t cap,
+                                size_t* out_len, uint32_t* off, uint32_t* form);
+/* The Update body marshalled directly: decode, the transform of `mode`, SetResourceVersion(rv), marshal -- no
+ * splicing.  The independent second implementation the splice is tested against, and what a caller without the
+ * descriptor has to do per write.  Results as gpudiff_upsert_body_host. */
+int gpudiff_update_body_host(const uint8_t* doc, size_t len, uint32_t mode, const uint8_t* rv, size_t rv_len,
+                             uint8_t* out, size_t cap, size_t* out_len);
+
 /* ---- Deployment splitter status roll-up ----
  * pkg/reconciler/deployment/deployment.go:41-91: when a leaf Deployment
  * changes, the splitter lists every cached Deployment labelled

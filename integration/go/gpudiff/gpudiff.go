@@ -16,6 +16,7 @@ import "C"
 
 import (
 	"bytes"
+	"encoding/json"
 	"errors"
 	"fmt"
 	"math"
@@ -973,13 +974,21 @@ const (
 // bytes of json.NewEncoder(w).Encode(obj.Object), built by kernel K10 (the
 // host path completes what K10 leaves).  bodies[i] is nil when objs[i] is not
 // an *unstructured.Unstructured or does not decode; the caller then takes the
-// reference path for that object.  The caller splices the live
-// resourceVersion in before client.Update (specsyncer.go:122,
-// statussyncer.go:56) exactly as today.
+// reference path for that object.  For client.Update the live
+// resourceVersion goes in first (specsyncer.go:122, statussyncer.go:56):
+// UpsertBodiesRV also returns where, and SpliceRV puts it there.
 func (e *Engine) UpsertBodies(objs []interface{}, mode Mode) ([][]byte, error) {
+	bodies, _, _, err := e.UpsertBodiesRV(objs, mode)
+	return bodies, err
+}
+
+// UpsertBodiesRV is UpsertBodies plus each body's resourceVersion splice descriptor
+// (gpudiff_bodies_rv_splice): SpliceRV(bodies[i], rvOff[i], rvForm[i], rv) is the Update body.
+// NOT COMPILED HERE, like the rest of this shim.
+func (e *Engine) UpsertBodiesRV(objs []interface{}, mode Mode) (bodies [][]byte, rvOff []uint32, rvForm []uint8, err error) {
 	n := len(objs)
 	if n == 0 {
-		return nil, nil
+		return nil, nil, nil, nil
 	}
 	docs := C.malloc(C.size_t(n) * C.size_t(unsafe.Sizeof(uintptr(0))))
 	lens := C.malloc(C.size_t(n) * C.size_t(unsafe.Sizeof(C.size_t(0))))
@@ -1003,20 +1012,69 @@ func (e *Engine) UpsertBodies(objs []interface{}, mode Mode) ([][]byte, error) {
 	var out C.gpudiff_bodies
 	if err := errOf(C.gpudiff_upsert_bodies(e.ctx, (**C.uint8_t)(docs), (*C.size_t)(lens), C.size_t(n),
 		C.uint32_t(mode), &out)); err != nil {
-		return nil, err
+		return nil, nil, nil, err
 	}
 	defer C.gpudiff_bodies_release(e.ctx, &out)
+	var rv C.gpudiff_rv_splice
+	if err := errOf(C.gpudiff_bodies_rv_splice(e.ctx, &out, &rv)); err != nil {
+		return nil, nil, nil, err
+	}
 	offs := (*[1 << 30]C.uint64_t)(unsafe.Pointer(out.offsets))[: n+1 : n+1]
 	st := (*[1 << 30]C.int32_t)(unsafe.Pointer(out.status))[:n:n]
 	res := make([][]byte, n)
+	rvOff, rvForm = make([]uint32, n), make([]uint8, n)
+	ro := (*[1 << 30]C.uint32_t)(unsafe.Pointer(rv.off))[:n:n]
+	rf := (*[1 << 30]C.uint8_t)(unsafe.Pointer(rv.form))[:n:n]
 	for i := 0; i < n; i++ {
 		if lp[i] == 0 || st[i] != 0 {
 			continue
 		}
 		res[i] = C.GoBytes(unsafe.Pointer(uintptr(unsafe.Pointer(out.bytes))+uintptr(offs[i])),
 			C.int(offs[i+1]-offs[i]))
+		rvOff[i], rvForm[i] = uint32(ro[i]), uint8(rf[i])
 	}
-	return res, nil
+	return res, rvOff, rvForm, nil
+}
+
+// The form of a resourceVersion splice descriptor (GPUDIFF_RV_*).
+const (
+	RVNone   = uint8(C.GPUDIFF_RV_NONE)   // no splice: the Update body is the body
+	RVInsert = uint8(C.GPUDIFF_RV_INSERT) // insert the member text at the offset
+	RVLead   = uint8(C.GPUDIFF_RV_LEAD)   // the text starts with ','
+	RVTrail  = uint8(C.GPUDIFF_RV_TRAIL)  // the text ends with ','
+	RVWrap   = uint8(C.GPUDIFF_RV_WRAP)   // the member is "metadata":{"resourceVersion":"<rv>"}
+)
+
+// SpliceRV returns the Update body: body with SetResourceVersion(rv) applied, by the descriptor the engine
+// returned with it (Write.RVOff / Write.RVForm, UpsertBodiesRV).  Pure Go, two copies around the member; rv is
+// escaped by encoding/json, i.e. exactly as the dynamic client would.  rv == "" or RVNone: body itself.  A
+// descriptor that does not fit the body (not the engine's) returns body unchanged.
+// NOT COMPILED HERE, like the rest of this shim.
+func SpliceRV(body []byte, off uint32, form uint8, rv string) []byte {
+	if rv == "" || form&RVInsert == 0 || off == 0 || int(off) >= len(body) {
+		return body
+	}
+	val, err := json.Marshal(rv) // HTML-safe, invalid UTF-8 as \ufffd: encodeState.string
+	if err != nil {
+		return body
+	}
+	out := make([]byte, 0, len(body)+len(val)+40)
+	out = append(out, body[:off]...)
+	if form&RVLead != 0 {
+		out = append(out, ',')
+	}
+	if form&RVWrap != 0 {
+		out = append(out, `"metadata":{`...)
+	}
+	out = append(out, `"resourceVersion":`...)
+	out = append(out, val...)
+	if form&RVWrap != 0 {
+		out = append(out, '}')
+	}
+	if form&RVTrail != 0 {
+		out = append(out, ',')
+	}
+	return append(out, body[off:]...)
 }
 
 // OptDeviceEncode opens an engine whose submits send raw JSON to the GPU (kernel K0); DiffAndPlan needs it.
@@ -1057,6 +1115,9 @@ type Write struct {
 	Kind Mode   // UpsertSpec or UpsertStatus
 	Noop bool   // the body equals the other document's on the wire in that region (GPUDIFF_SPEC_NOOP / _STATUS_NOOP)
 	Body []byte // the request body; nil for a no-op, or when Go cannot decode the object (reference path)
+	// where the live resourceVersion goes for client.Update / UpdateStatus: SpliceRV(Body, RVOff, RVForm, rv)
+	RVOff  uint32
+	RVForm uint8
 }
 
 // Plan modes (GPUDIFF_PLAN_*): which writes DiffAndPlanMode lists and which document they render.
@@ -1131,11 +1192,21 @@ func writesOf(plan *C.gpudiff_write_plan) []Write {
 	noop := (*[1 << 30]C.uint8_t)(unsafe.Pointer(plan.noop))[:m:m]
 	offs := (*[1 << 30]C.uint64_t)(unsafe.Pointer(plan.bodies.offsets))[: m+1 : m+1]
 	st := (*[1 << 30]C.int32_t)(unsafe.Pointer(plan.bodies.status))[:m:m]
+	var rv C.gpudiff_rv_splice
+	var ro []C.uint32_t
+	var rf []C.uint8_t
+	if C.gpudiff_bodies_rv_splice(nil, &plan.bodies, &rv) == C.GPUDIFF_OK {
+		ro = (*[1 << 30]C.uint32_t)(unsafe.Pointer(rv.off))[:m:m]
+		rf = (*[1 << 30]C.uint8_t)(unsafe.Pointer(rv.form))[:m:m]
+	}
 	for k := 0; k < m; k++ {
 		w := Write{Pair: int(idx[k]), Kind: Mode(kind[k]), Noop: noop[k] != 0}
 		if !w.Noop && st[k] == 0 {
 			w.Body = C.GoBytes(unsafe.Pointer(uintptr(unsafe.Pointer(plan.bodies.bytes))+uintptr(offs[k])),
 				C.int(offs[k+1]-offs[k]))
+			if ro != nil {
+				w.RVOff, w.RVForm = uint32(ro[k]), uint8(rf[k])
+			}
 		}
 		writes[k] = w
 	}

@@ -36,6 +36,7 @@
 #include "pathstr.h"
 #include "plan.h"
 #include "scan64.h"
+#include "store_plan.h"
 #include "values.h"
 
 #include <emmintrin.h>
@@ -1787,7 +1788,7 @@ int dstore_write_plan(gpudiff_ctx* c, DStore* s, gpudiff_ticket t, uint32_t kind
     if (timing) HIPCHK(hipEventRecord(R.pl_ev[3], st));
     if (timing) HIPCHK(hipEventRecord(R.pl_ev[4], st));
     HIPCHK(launch_body_lens(st, R.pl_wdoc, R.pl_touts, (uint32_t)nw, (uint32_t)ndocs, R.pl_lens,
-                            (int32_t*)(R.pl_head + H.off_k10), R.pl_tiles, R.pl_rec + 8));
+                            (uint32_t*)(R.pl_head + H.off_k10), R.pl_tiles, R.pl_rec + 8));
     uint64_t total = 0;
     HIPCHK(hipMemcpyAsync(&total, R.pl_rec + 8, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
@@ -1809,6 +1810,22 @@ int dstore_write_plan(gpudiff_ctx* c, DStore* s, gpudiff_ticket t, uint32_t kind
     HIPCHK(hipStreamSynchronize(st));
     S.d2h_bytes += H.bytes + total;
     if (out->offsets[nw] != total) return GPUDIFF_E_DEVICE;  // the offsets the bodies were packed by
+    // K10's verdict words, in place: the statuses where they came back, the splice points beside them
+    try {
+        out->rv_off_v.resize(nw);
+        out->rv_form_v.resize(nw);
+    } catch (const std::bad_alloc&) {
+        return GPUDIFF_E_NOMEM;
+    }
+    int32_t* const k10 = (int32_t*)((uint8_t*)out->words.data() + H.off_k10);
+    for (uint64_t w = 0; w < nw; w++) {
+        uint32_t ro, rf;
+        plan_k10_unpack((uint32_t)k10[w], &k10[w], &ro, &rf);
+        out->rv_off_v[w] = ro;
+        out->rv_form_v[w] = (uint8_t)rf;
+    }
+    out->rv_off = out->rv_off_v.data();
+    out->rv_form = out->rv_form_v.data();
     // 4. K10's deferrals: their JSON gathered from djson on the device, one copy back (the caller's event buffers
     //    are not read: they are only valid until gpudiff_wait)
     const TokDoc* hdocs = (const TokDoc*)R.hmeta;

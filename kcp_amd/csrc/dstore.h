@@ -41,15 +41,21 @@ int dstore_staged_mark_read(gpudiff_ctx* c, gpudiff_ticket t);
 // the host (gathered on the device, one copy back).  upsert.cpp marshals those and wraps the result.
 struct StorePlan {
     size_t n = 0;                  // writes
-    std::vector<uint64_t> words;   // offsets[n + 1] | pair_index[n] | src_doc[n] | k10[n] | kind[n] | noop[n] | pad | bytes
+    // offsets[n + 1] | pair_index[n] | src_doc[n] | k10[n] | kind[n] | noop[n] | pad | bytes; k10[] comes back as
+    // K10's verdict words (store_plan.h plan_k10_word) and is unpacked in place, the splice points into rv_*_v
+    std::vector<uint64_t> words;
     const uint64_t* offsets = nullptr;    // dense: body w = bytes[offsets[w], offsets[w + 1]); empty unless K10 rendered it
     const uint32_t* pair_index = nullptr;
     const uint32_t* src_doc = nullptr;
     const int32_t* k10 = nullptr;         // GPUDIFF_TOK_*; not OK: the host renders the body
     const uint8_t* kind = nullptr;
     const uint8_t* noop = nullptr;
+    const uint32_t* rv_off = nullptr;     // K10's resourceVersion splice point per write (GPUDIFF_RV_*; a write
+    const uint8_t* rv_form = nullptr;     // without a device body: 0 / GPUDIFF_RV_NONE)
     const uint8_t* bytes = nullptr;
-    std::vector<uint32_t> def;     // the writes whose document K10 left to the host, ascending
+    std::vector<uint32_t> rv_off_v;
+    std::vector<uint8_t> rv_form_v;
+    std::vector<uint32_t> def;    // the writes whose document K10 left to the host, ascending
     std::vector<uint8_t> hjson;    // their documents' JSON: write def[k]'s at hjson[hoff[k]], hlen[k] bytes
     std::vector<uint64_t> hoff;
     std::vector<uint32_t> hlen;

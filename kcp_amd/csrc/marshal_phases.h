@@ -25,6 +25,8 @@
 //      rank) and one exclusive scan over all of them, so a member's offset
 //      in its container is a difference of two prefix values
 //   M8 value offsets top-down by depth, visibility
+//   M8b the byte offset at which the Update body's `"resourceVersion":"<rv>"` goes, and its commas (marks from M2,
+//      ends gathered by M9, settled after it)
 //   M9 emit: every visible node writes its comma, key and value text
 // Anything outside this subset keeps a nonzero status and the host marshals
 // the document (upsert.cpp, the Go-exact path).
@@ -189,7 +191,8 @@ __device__ __forceinline__ void marshal_m1_floats(const DocTree& T, const Marsha
 
 // ---------------------------------------------------------- M2-M4 transform marks, child lists, owner references
 // mmode: GPUDIFF_UPSERT_* (owner references are normalized in spec mode only)
-__device__ __forceinline__ void marshal_m2_m4_children(const DocTree& T, const MarshalScratch& M, uint32_t mmode,
+// Returns whether the root has a "metadata" member that is no object (the Update body then takes no splice).
+__device__ __forceinline__ bool marshal_m2_m4_children(const DocTree& T, const MarshalScratch& M, uint32_t mmode,
                                                        uint32_t& status) {
     const uint8_t* const d = T.d;
     const uint32_t lane = T.lane, nn = T.nn, meta_node = T.meta_node, labels_node = T.labels_node;
@@ -197,8 +200,10 @@ __device__ __forceinline__ void marshal_m2_m4_children(const DocTree& T, const M
     const Scratch& S = T.S;
     // ---------------------------------------------------------- M2 transform marks, child counts
     uint32_t orf = NONE, owned = NONE;
+    bool meta_other = false;
     if (status == GPUDIFF_TOK_OK) {
         uint32_t my_orf = NONE, my_owned = NONE;
+        bool my_meta_other = false;
         for (uint32_t i0 = 1; i0 < nn; i0 += 64) {
             const uint32_t i = i0 + lane;
             if (i >= nn) break;
@@ -206,8 +211,18 @@ __device__ __forceinline__ void marshal_m2_m4_children(const DocTree& T, const M
             atomicAdd(&M.nch[r.x], 1u);
             if (r.x == meta_node && meta_node != NONE) {
                 const KeyWin K = key_win(T, r.y);
-                if (field_fold(K, "uid", 3) == 1u || field_fold(K, "resourceVersion", 15) == 1u) M.fl[i] = MF_HIDDEN;
-                else if (mmode == GPUDIFF_UPSERT_SPEC && field_fold(K, "ownerReferences", 15) == 1u) my_orf = i;
+                if (field_fold(K, "uid", 3) == 1u || field_fold(K, "resourceVersion", 15) == 1u) {
+                    M.fl[i] = MF_HIDDEN;
+                } else {
+                    if (mmode == GPUDIFF_UPSERT_SPEC && field_fold(K, "ownerReferences", 15) == 1u) my_orf = i;
+                    if (key_win_cmp(K, "resourceVersion", 15) < 0) M.fl[i] |= MF_RVPRE;  // for M9's splice point
+                }
+            } else if (meta_node == NONE && r.x == 0u) {
+                // no metadata object: the splice wraps the member into a "metadata" member of the root -- unless
+                // the root has that key with another kind of value (SetNestedField fails, nothing is set)
+                const int c = key_win_cmp(key_win(T, r.y), "metadata", 8);
+                if (c < 0) M.fl[i] |= MF_RVPRE;
+                my_meta_other |= c == 0;
             }
             if (r.x == labels_node && labels_node != NONE && labels_ok && (r.w & NI_STR)) {
                 if (field_fold(key_win(T, r.y), "kcp.dev/owned-by", 16) == 1u) my_owned = i;
@@ -216,6 +231,7 @@ __device__ __forceinline__ void marshal_m2_m4_children(const DocTree& T, const M
         // duplicate keys are resolved (deferred) by M5 before anything is emitted
         orf = wave_min_v(my_orf);
         owned = wave_min_v(my_owned);
+        if (meta_node == NONE) meta_other = ballot(my_meta_other) != 0;
     }
     wave_sync();
 
@@ -318,6 +334,7 @@ __device__ __forceinline__ void marshal_m2_m4_children(const DocTree& T, const M
         if (drop && lane == 0) M.fl[orf] = MF_HIDDEN;
     }
     wave_sync();
+    return meta_other;
 }
 
 // ---------------------------------------------------------- M5 sibling ranks
@@ -518,13 +535,46 @@ __device__ __forceinline__ uint32_t marshal_m6_m8_layout(const DocTree& T, const
     return sz0;
 }
 
+// ---------------------------------------------------------- M8b the resourceVersion splice point
+// Where `"resourceVersion":"<rv>"` goes in the body M9 writes (include/gpudiff.h GPUDIFF_RV_*): the Update body is
+// then two copies around that member, with no second marshal.  The member belongs in metadata (an object:
+// T.meta_node, `{}` included), or -- when the root has no "metadata" key -- inside a new `"metadata":{...}` member
+// of the root; a metadata that is present and not an object takes no splice (meta_other, from M2).
+//
+// Either way the place is the end of the last visible member of the container whose key sorts before the literal,
+// else just past the container's `{`.  M2 marked those members (MF_RVPRE: it holds their keys in registers anyway,
+// KeyWin, and compares the first 16 bytes as two big-endian words); M9, which visits every visible node with its
+// value's start in hand, keeps the largest end among the marked ones (rv_end: the layout grows with the rank, so
+// the last one is the maximum).  Hidden members (uid, resourceVersion, removed owner references) are never
+// visited, so they do not count.  What is left here is a wave maximum and two words of the container.
+__device__ __forceinline__ void marshal_m8b_rv_splice(const DocTree& T, const MarshalScratch& M, bool meta_other,
+                                                      uint32_t rv_end, uint32_t& off, uint32_t& form) {
+    const bool wrap = T.meta_node == NONE;
+    const uint32_t cont = wrap ? 0u : T.meta_node;  // the container the member text goes into
+    const uint32_t open = M.vst[cont], cfl = M.fl[cont];
+    const uint32_t end = wave_max_v(rv_end);
+    off = 0;
+    form = GPUDIFF_RV_NONE;
+    if (meta_other) return;
+    form = GPUDIFF_RV_INSERT | (wrap ? GPUDIFF_RV_WRAP : 0u);
+    if (end) {
+        off = end;
+        form |= GPUDIFF_RV_LEAD;
+    } else {
+        off = open + 1u;
+        if (cfl & MF_HASVIS) form |= GPUDIFF_RV_TRAIL;
+    }
+}
+
 // ---------------------------------------------------------- M9 emit
-// dst: the body's place; sz0, any_float: from M6-M8 and M1
-__device__ __forceinline__ void marshal_m9_emit(const DocTree& T, const MarshalScratch& M, uint8_t* dst, uint32_t sz0,
-                                                bool any_float) {
+// dst: the body's place; sz0, any_float: from M6-M8 and M1.  Returns this lane's part of M8b: the largest end of a
+// visible MF_RVPRE member's value it wrote (0: none).
+__device__ __forceinline__ uint32_t marshal_m9_emit(const DocTree& T, const MarshalScratch& M, uint8_t* dst,
+                                                    uint32_t sz0, bool any_float) {
     const uint8_t* const d = T.d;
     const uint32_t lane = T.lane, nn = T.nn;
     const Scratch& S = T.S;
+    uint32_t rv_end = 0;
     if (lane == 0) {
         dst[0] = '{';
         dst[sz0 - 1] = '}';
@@ -545,6 +595,7 @@ __device__ __forceinline__ void marshal_m9_emit(const DocTree& T, const MarshalS
         const uint32_t vs = M.vst[i], ksz = M.ksz[i];
         const uint32_t kpos = vs - ksz;
         if (kpos != M.vst[r.x] + 1u) dst[kpos - 1] = ',';
+        if (fl & MF_RVPRE) rv_end = max(rv_end, vs + M.sz[i]);
         if (ksz) {
             const uint8_t* kp;
             const uint32_t kl = key_of(T, r.y, &kp);
@@ -658,6 +709,7 @@ __device__ __forceinline__ void marshal_m9_emit(const DocTree& T, const MarshalS
             }
         }
     }
+    return rv_end;
 }
 
 // T: the document's tree; work: the document's working area (marshal_layout); mmode: GPUDIFF_UPSERT_*; bodies +
@@ -673,15 +725,18 @@ __device__ __forceinline__ void marshal_doc(const DocTree& T, uint8_t* work, uin
     mark(PM_M1);
     if (status == GPUDIFF_TOK_OK && any_float) marshal_m1_floats(T, M);
     mark(PM_M1_FLOATS);
-    marshal_m2_m4_children(T, M, mmode, status);
+    const bool meta_other = marshal_m2_m4_children(T, M, mmode, status);
     mark(PM_M2_M4);
     marshal_m5_ranks(T, M, status);
     mark(PM_M5);
     const uint32_t sz0 = marshal_m6_m8_layout(T, M, lds, marshal_out_cap(T.len), status);
     mark(PM_M6_M8);
     if (status == GPUDIFF_TOK_OK) {
-        marshal_m9_emit(T, M, bodies + obase, sz0, any_float);
+        const uint32_t rv_end = marshal_m9_emit(T, M, bodies + obase, sz0, any_float);
         o.bytes = sz0 + 1u;
+        uint32_t rv_off, rv_form;
+        marshal_m8b_rv_splice(T, M, meta_other, rv_end, rv_off, rv_form);
+        tokout_set_rv_splice(o, rv_off, rv_form);
     }
     o.n_nodes = T.nn;
     o.status = status;

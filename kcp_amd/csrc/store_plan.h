@@ -62,6 +62,25 @@ __host__ __device__ inline uint8_t plan_final_flags(uint8_t pass_flags, uint8_t 
     return f;
 }
 
+// K10's verdict per write, one word in the write list that comes back (k_body_lens packs, dstore_write_plan unpacks):
+// a status other than GPUDIFF_TOK_OK as it is -- the host renders that body and works out its own descriptor -- else
+// bit 31 with the body's resourceVersion splice point (include/gpudiff.h GPUDIFF_RV_*): the form in bits 26-29, the
+// body-relative offset in bits 0-25.  The word the status alone used to take, so the list stays 22 B a write.
+constexpr uint32_t kPlanRvBit = 1u << 31, kPlanRvFormShift = 26, kPlanRvOffMask = (1u << kPlanRvFormShift) - 1u;
+static_assert(2ull * kTokMaxLen + 512u + 15u <= kPlanRvOffMask, "an offset inside marshal_out_cap(len) fits 26 bits");
+static_assert(((GPUDIFF_RV_INSERT | GPUDIFF_RV_LEAD | GPUDIFF_RV_TRAIL | GPUDIFF_RV_WRAP) << kPlanRvFormShift) <
+                  kPlanRvBit, "the form fits below bit 31");
+__host__ __device__ inline uint32_t plan_k10_word(uint32_t status, uint32_t rv_off, uint32_t rv_form) {
+    return status != GPUDIFF_TOK_OK ? status & ~kPlanRvBit
+                                    : kPlanRvBit | (rv_form << kPlanRvFormShift) | (rv_off & kPlanRvOffMask);
+}
+__host__ __device__ inline void plan_k10_unpack(uint32_t word, int32_t* status, uint32_t* rv_off, uint32_t* rv_form) {
+    const bool ok = (word & kPlanRvBit) != 0u || word == GPUDIFF_TOK_OK;
+    *status = ok ? (int32_t)GPUDIFF_TOK_OK : (int32_t)word;
+    *rv_off = ok ? word & kPlanRvOffMask : 0u;
+    *rv_form = ok ? (word & ~kPlanRvBit) >> kPlanRvFormShift : (uint32_t)GPUDIFF_RV_NONE;
+}
+
 // K19's copy of one body, this lane's share (lane of 64): n bytes from src to dst, both of any alignment.
 // Dword granularity: the bytes up to dst's first 4-B boundary and behind its last one go as single bytes, every
 // dword between is one aligned 4-B store built from the one or two aligned source dwords that hold its bytes.

@@ -1172,6 +1172,8 @@ __device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
 }
 constexpr uint32_t MF_HIDDEN = 1u, MF_CUSTOM = 2u, MF_HASVIS = 4u, MF_VIS = 8u, MF_FLOAT = 16u;
 constexpr uint32_t MF_VCLEAN = 32u, MF_KCLEAN = 64u;  // string value / key written as its own bytes
+// a member of the container the Update body's resourceVersion member goes into, whose key sorts before that member's
+constexpr uint32_t MF_RVPRE = 128u;
 constexpr uint32_t kMarshalMaxMembers = 2048;
 constexpr int kModeEncode = 0, kModeMarshal = 1, kModeRollup = 2, kModeNegotiate = 3;
 
@@ -1213,6 +1215,23 @@ __device__ __forceinline__ uint32_t field_fold(const KeyWin& K, const char* name
         nonfold |= x & ~lm;
     }
     return diff == 0ull ? 1u : nonfold == 0ull ? 2u : 0u;
+}
+// Go string order (bytes, then length) of the key against a name of at most 16 bytes, from the same window: -1, 0, 1.
+// Each 8-byte word big-endian and zero padded past the key's end: keys on the device hold no escapes, hence no 0
+// byte, so the padded words order the strings, and equal words mean equal bytes.
+__device__ __forceinline__ int key_win_cmp(const KeyWin& K, const char* name, uint32_t nl) {
+#pragma unroll
+    for (uint32_t j = 0; j < 2; j++) {
+        uint64_t nw = 0;
+#pragma unroll
+        for (uint32_t b = 0; b < 8; b++)
+            if (8u * j + b < nl) nw |= (uint64_t)(uint8_t)name[8u * j + b] << (8u * (7u - b));
+        const uint32_t kb = K.kl > 8u * j ? K.kl - 8u * j : 0u;
+        const uint64_t kw = kb >= 8u ? K.w[j] : K.w[j] & ((1ull << (8u * kb)) - 1ull);
+        const uint64_t kbe = __builtin_bswap64(kw);
+        if (kbe != nw) return kbe < nw ? -1 : 1;
+    }
+    return K.kl > 16u ? 1 : 0;  // equal through 16 bytes: the name has ended
 }
 // appsv1.DeploymentStatus counters summed by deployment.go:79-85, in RollOut.v order
 __device__ __forceinline__ const char* roll_field(uint32_t k) {

@@ -50,6 +50,15 @@ __host__ __device__ inline uint64_t tokdoc_marshal_off(const TokDoc& t) {
 __host__ __device__ inline void tokdoc_set_neg_kind(TokDoc& t, uint32_t kind) { t.pad[0] = kind; }
 __host__ __device__ inline uint32_t tokdoc_neg_kind(const TokDoc& t) { return t.pad[0]; }
 static_assert(sizeof(TokOut) == 48, "TokOut");
+// TokOut by mode.  K10 (marshal) leaves the segment fields unused and reports the body's resourceVersion splice
+// point (include/gpudiff.h GPUDIFF_RV_*) in two of them: spec_l = the byte offset from the body's first byte,
+// spec_ar = the form.  Both 0 unless status is GPUDIFF_TOK_OK.
+__host__ __device__ inline void tokout_set_rv_splice(TokOut& o, uint32_t off, uint32_t form) {
+    o.spec_l = off;
+    o.spec_ar = form;
+}
+__host__ __device__ inline uint32_t tokout_rv_off(const TokOut& o) { return o.spec_l; }
+__host__ __device__ inline uint32_t tokout_rv_form(const TokOut& o) { return o.spec_ar; }
 
 __host__ __device__ inline uint64_t tok_align(uint64_t x) { return (x + 255u) & ~(uint64_t)255u; }
 __host__ __device__ inline uint32_t tok_cap(uint32_t len) { return len + 2u; }

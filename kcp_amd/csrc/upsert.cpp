@@ -32,6 +32,14 @@
 
 using namespace gd;
 
+namespace gd {
+// a body's resourceVersion splice point (include/gpudiff.h GPUDIFF_RV_*)
+struct RvSplice {
+    uint32_t off = 0;
+    uint32_t form = GPUDIFF_RV_NONE;
+};
+}  // namespace gd
+
 namespace {
 
 const char kHex[] = "0123456789abcdef";
@@ -239,45 +247,134 @@ bool put_owner_refs(std::string& o, const Node& refs, const char* owned, size_t 
 
 }  // namespace
 
-namespace gd {
+namespace {
 
-// The body for one decoded object (root: a J_OBJ).
-void upsert_body(const Node& root, uint32_t mode, std::string& o) {
-    o.clear();
-    const Member* md = find(root, "metadata");
-    if (!md || md->v.t != J_OBJ) {
-        put_object(o, root);  // RemoveNestedField / SetNestedField: no-ops without a metadata map
-        o.push_back('\n');
-        return;
+// Go string order of a member's key against a literal
+int key_cmp(const Member* m, const char* lit) {
+    const size_t ll = strlen(lit);
+    const int c = memcmp(m->k, lit, std::min<size_t>(m->klen, ll));
+    return c != 0 ? c : m->klen < ll ? -1 : m->klen > ll ? 1 : 0;
+}
+
+// the kcp.dev/owned-by label of a metadata map: GetLabels() is NestedStringMap (nil unless every value is a string)
+void owned_by(const Node& md, const char** owned, size_t* owned_len) {
+    *owned = "";
+    *owned_len = 0;
+    const Member* lb = find(md, "labels");
+    if (!lb || lb->v.t != J_OBJ) return;
+    for (uint32_t i = 0; i < lb->v.n; i++)
+        if (lb->v.u.mem[i].v.t != J_STR) return;
+    if (const Member* ob = find(lb->v, "kcp.dev/owned-by")) {
+        *owned = ob->v.u.s;
+        *owned_len = ob->v.n;
     }
-    // owned-by: GetLabels() is NestedStringMap (nil unless every value is a string)
-    const char* owned = "";
-    size_t owned_len = 0;
-    if (mode == GPUDIFF_UPSERT_SPEC) {
-        const Member* lb = find(md->v, "labels");
-        if (lb && lb->v.t == J_OBJ) {
-            bool all_str = true;
-            for (uint32_t i = 0; i < lb->v.n; i++)
-                if (lb->v.u.mem[i].v.t != J_STR) all_str = false;
-            const Member* ob = all_str ? find(lb->v, "kcp.dev/owned-by") : nullptr;
-            if (ob) {
-                owned = ob->v.u.s;
-                owned_len = ob->v.n;
-            }
+}
+
+// Where a member with a given key goes in the object being written (include/gpudiff.h GPUDIFF_RV_*): fed each
+// emitted member in key order, it keeps the end of the last one that sorts before the key.
+struct SplicePoint {
+    size_t open = 0;  // just past the container's '{'
+    size_t before_end = 0;
+    bool before = false, after = false;
+    void member(int cmp, size_t end) {
+        if (cmp < 0) {
+            before = true;
+            before_end = end;
+        } else {
+            after = true;
         }
     }
+    RvSplice done(uint32_t extra) const {
+        RvSplice s;
+        s.form = GPUDIFF_RV_INSERT | extra;
+        if (before) {
+            s.off = (uint32_t)before_end;
+            s.form |= GPUDIFF_RV_LEAD;
+        } else {
+            s.off = (uint32_t)open;
+            if (after) s.form |= GPUDIFF_RV_TRAIL;
+        }
+        return s;
+    }
+};
+
+// encodeState.string(s, escapeHTML = true) of Go 1.16 over arbitrary bytes: what put_str writes for valid UTF-8,
+// and "\ufffd" for every byte utf8.DecodeRuneInString rejects (RuneError, width 1)
+void put_go_str(std::string& o, const uint8_t* s, size_t n) {
+    o.push_back('"');
+    for (size_t i = 0; i < n;) {
+        const uint8_t c = s[i];
+        if (c < 0x80) {  // put_str's ASCII rules, without its quotes
+            const char one = (char)c;
+            std::string t;
+            put_str(t, &one, 1);
+            o.append(t, 1, t.size() - 2);
+            i++;
+            continue;
+        }
+        // utf8.DecodeRune's acceptance: the lead byte's length and the second byte's range
+        size_t need = 0;
+        uint8_t lo = 0x80, hi = 0xBF;
+        if (c >= 0xC2 && c <= 0xDF) need = 1;
+        else if (c >= 0xE0 && c <= 0xEF) {
+            need = 2;
+            if (c == 0xE0) lo = 0xA0;
+            if (c == 0xED) hi = 0x9F;
+        } else if (c >= 0xF0 && c <= 0xF4) {
+            need = 3;
+            if (c == 0xF0) lo = 0x90;
+            if (c == 0xF4) hi = 0x8F;
+        }
+        bool ok = need != 0 && need < n - i;  // the whole sequence lies inside the string
+        if (ok) {
+            if (s[i + 1] < lo || s[i + 1] > hi) ok = false;
+            for (size_t k = 2; ok && k <= need; k++)
+                if (s[i + k] < 0x80 || s[i + k] > 0xBF) ok = false;
+        }
+        if (!ok) {
+            o += "\\ufffd";
+            i++;
+        } else if (c == 0xE2 && s[i + 1] == 0x80 && (s[i + 2] == 0xA8 || s[i + 2] == 0xA9)) {
+            o += "\\u202";
+            o.push_back(s[i + 2] == 0xA8 ? '8' : '9');
+            i += 3;
+        } else {
+            o.append((const char*)s + i, need + 1);
+            i += need + 1;
+        }
+    }
+    o.push_back('"');
+}
+
+}  // namespace
+
+namespace gd {
+
+// The body for one decoded object (root: a J_OBJ); *sp (optional) = where its resourceVersion member would go.
+void upsert_body(const Node& root, uint32_t mode, std::string& o, RvSplice* sp) {
+    o.clear();
+    const Member* md = find(root, "metadata");
+    const bool md_map = md && md->v.t == J_OBJ;
+    // RemoveNestedField / SetNestedField are no-ops without a metadata map
+    const char* owned = "";
+    size_t owned_len = 0;
+    if (md_map && mode == GPUDIFF_UPSERT_SPEC) owned_by(md->v, &owned, &owned_len);
+    SplicePoint root_pt, meta_pt;
     o.push_back('{');
+    root_pt.open = o.size();
     bool first = true;
     for (const Member* m : sorted_members(root)) {
         if (!first) o.push_back(',');
         first = false;
         put_str(o, m->k, m->klen);
         o.push_back(':');
-        if (m != md) {
+        if (m != md || !md_map) {
             put_value(o, m->v);
+            root_pt.member(key_cmp(m, "metadata"), o.size());
             continue;
         }
         o.push_back('{');
+        meta_pt.open = o.size();
         bool f2 = true;
         for (const Member* x : sorted_members(md->v)) {
             auto is = [&](const char* k) { return x->klen == strlen(k) && memcmp(x->k, k, x->klen) == 0; };
@@ -293,10 +390,68 @@ void upsert_body(const Node& root, uint32_t mode, std::string& o) {
             }
             o += item;
             f2 = false;
+            meta_pt.member(key_cmp(x, "resourceVersion"), o.size());
         }
         o.push_back('}');
     }
     o.push_back('}');
+    o.push_back('\n');
+    if (sp) *sp = md_map ? meta_pt.done(0) : md ? RvSplice{} : root_pt.done(GPUDIFF_RV_WRAP);
+}
+
+// The Update body for one decoded object: the transform of `mode`, then SetResourceVersion(rv) =
+// SetNestedField(obj, rv, "metadata", "resourceVersion"), then the marshal -- written as that: the members of the
+// map the field is set in are rendered one by one, the new member joins them, and they are written in key order.
+void update_body(const Node& root, uint32_t mode, const uint8_t* rv, size_t rv_len, std::string& o) {
+    const Member* md = find(root, "metadata");
+    if (!rv_len || (md && md->v.t != J_OBJ)) {  // RemoveNestedField; SetNestedField's error, dropped
+        upsert_body(root, mode, o, nullptr);
+        return;
+    }
+    struct Item {
+        std::string key, text;
+    };
+    auto put_items = [](std::string& out, std::vector<Item>& items) {
+        std::sort(items.begin(), items.end(), [](const Item& a, const Item& b) { return a.key < b.key; });
+        out.push_back('{');
+        for (size_t i = 0; i < items.size(); i++) {
+            if (i) out.push_back(',');
+            put_str(out, items[i].key.data(), items[i].key.size());
+            out.push_back(':');
+            out += items[i].text;
+        }
+        out.push_back('}');
+    };
+    std::vector<Item> meta;
+    if (md) {
+        const char* owned = "";
+        size_t owned_len = 0;
+        if (mode == GPUDIFF_UPSERT_SPEC) owned_by(md->v, &owned, &owned_len);
+        for (uint32_t i = 0; i < md->v.n; i++) {
+            const Member& x = md->v.u.mem[i];
+            Item it{std::string(x.k, x.klen), std::string()};
+            if (it.key == "uid" || it.key == "resourceVersion") continue;
+            if (mode == GPUDIFF_UPSERT_SPEC && it.key == "ownerReferences") {
+                if (!put_owner_refs(it.text, x.v, owned, owned_len)) continue;
+            } else {
+                put_value(it.text, x.v);
+            }
+            meta.push_back(std::move(it));
+        }
+    }
+    meta.push_back(Item{"resourceVersion", std::string()});
+    put_go_str(meta.back().text, rv, rv_len);
+    std::vector<Item> top;
+    for (uint32_t i = 0; i < root.n; i++) {
+        const Member& m = root.u.mem[i];
+        if (&m == md) continue;
+        top.push_back(Item{std::string(m.k, m.klen), std::string()});
+        put_value(top.back().text, m.v);
+    }
+    top.push_back(Item{"metadata", std::string()});
+    put_items(top.back().text, meta);
+    o.clear();
+    put_items(o, top);
     o.push_back('\n');
 }
 
@@ -318,6 +473,10 @@ struct BodiesStore {
     std::vector<uint8_t> bytes;
     std::vector<int32_t> status, k10;
     std::vector<uint8_t> source;
+    // per body, where its resourceVersion member goes (gpudiff_bodies_rv_splice), and who computed it
+    std::vector<uint32_t> rv_off;
+    std::vector<uint8_t> rv_form;
+    size_t rv_device = 0, rv_host = 0;
 };
 
 void publish(BodiesStore* bs, gpudiff_bodies* out, size_t n, size_t n_host) {
@@ -337,6 +496,7 @@ struct Body {
     enum Kind { kNone, kDevice, kHost, kDecodeError } kind;
     const uint8_t* p;
     size_t n;
+    RvSplice rv;  // of a kDevice / kHost body: K10's (TokOut) or the host marshaller's
 };
 
 // offsets / bytes / status / source of bs for nw writes.  body_of(w) is called exactly once per write, for
@@ -346,29 +506,50 @@ void assemble_bodies(BodiesStore* bs, size_t nw, F&& body_of) {
     bs->offsets.resize(nw + 1);
     bs->status.assign(nw, 0);
     bs->source.assign(nw, GPUDIFF_BODY_DEVICE);
+    bs->rv_off.assign(nw, 0);
+    bs->rv_form.assign(nw, GPUDIFF_RV_NONE);
     for (size_t w = 0; w < nw; w++) {
         bs->offsets[w] = bs->bytes.size();
         const Body b = body_of(w);
         if (b.kind == Body::kHost || b.kind == Body::kDecodeError) bs->source[w] = GPUDIFF_BODY_HOST;
         if (b.kind == Body::kDecodeError) bs->status[w] = GPUDIFF_E_DECODE;
         else if (b.kind != Body::kNone) bs->bytes.insert(bs->bytes.end(), b.p, b.p + b.n);
+        if (b.kind == Body::kDevice || b.kind == Body::kHost) {
+            bs->rv_off[w] = b.rv.off;
+            bs->rv_form[w] = (uint8_t)b.rv.form;
+            (b.kind == Body::kDevice ? bs->rv_device : bs->rv_host)++;
+        }
     }
     bs->offsets[nw] = bs->bytes.size();
 }
 
 // the host path's answer for one deferred write
-Body host_body_of(const std::string& body, bool ok) {
-    return ok ? Body{Body::kHost, (const uint8_t*)body.data(), body.size()} : Body{Body::kDecodeError, nullptr, 0};
+Body host_body_of(const std::string& body, bool ok, const RvSplice& rv) {
+    return ok ? Body{Body::kHost, (const uint8_t*)body.data(), body.size(), rv}
+              : Body{Body::kDecodeError, nullptr, 0, RvSplice{}};
 }
 
-// host marshal of one document into o; false = Go decode error
-bool host_body(const uint8_t* doc, size_t len, uint32_t mode, std::string& o) {
+// K10's answer for one write: the body's bytes in `raw` and the descriptor in its TokOut
+Body device_body_of(const uint8_t* raw, const TokOut& t) {
+    return Body{Body::kDevice, raw + t.off, t.bytes, RvSplice{tokout_rv_off(t), tokout_rv_form(t)}};
+}
+
+// host marshal of one document into o, its splice point into *rv; false = Go decode error
+bool host_body(const uint8_t* doc, size_t len, uint32_t mode, std::string& o, RvSplice* rv) {
     JsonParser jp;
     Arena arena;
     Node root;
     if (!jp.parse_object(doc, len, arena, &root)) return false;
-    upsert_body(root, mode, o);
+    upsert_body(root, mode, o, rv);
     return true;
+}
+
+// a host-only entry point's result into the caller's buffer
+int give(const std::string& o, uint8_t* out, size_t cap, size_t* out_len) {
+    *out_len = o.size();
+    if (o.size() > cap || (!out && o.size())) return GPUDIFF_E_CAPACITY;
+    if (o.size()) memcpy(out, o.data(), o.size());
+    return GPUDIFF_OK;
 }
 
 }  // namespace
@@ -377,15 +558,75 @@ extern "C" {
 
 int gpudiff_upsert_body_host(const uint8_t* doc, size_t len, uint32_t mode, uint8_t* out, size_t cap,
                              size_t* out_len) {
-    if ((!doc && len) || !out_len || mode > GPUDIFF_UPSERT_STATUS) return GPUDIFF_E_INVAL;
+    uint32_t off, form;
+    return gpudiff_upsert_body_host_rv(doc, len, mode, out, cap, out_len, &off, &form);
+}
+
+int gpudiff_upsert_body_host_rv(const uint8_t* doc, size_t len, uint32_t mode, uint8_t* out, size_t cap,
+                                size_t* out_len, uint32_t* off, uint32_t* form) {
+    if ((!doc && len) || !out_len || !off || !form || mode > GPUDIFF_UPSERT_STATUS) return GPUDIFF_E_INVAL;
     std::string o;
-    if (!host_body(doc ? doc : (const uint8_t*)"", len, mode, o)) {
+    RvSplice rv;
+    *off = 0;
+    *form = GPUDIFF_RV_NONE;
+    if (!host_body(doc ? doc : (const uint8_t*)"", len, mode, o, &rv)) {
         *out_len = 0;
         return GPUDIFF_E_DECODE;
     }
-    *out_len = o.size();
-    if (o.size() > cap || (!out && o.size())) return GPUDIFF_E_CAPACITY;
-    if (o.size()) memcpy(out, o.data(), o.size());
+    *off = rv.off;
+    *form = rv.form;
+    return give(o, out, cap, out_len);
+}
+
+int gpudiff_update_body_host(const uint8_t* doc, size_t len, uint32_t mode, const uint8_t* rv, size_t rv_len,
+                             uint8_t* out, size_t cap, size_t* out_len) {
+    if ((!doc && len) || (!rv && rv_len) || !out_len || mode > GPUDIFF_UPSERT_STATUS) return GPUDIFF_E_INVAL;
+    JsonParser jp;
+    Arena arena;
+    Node root;
+    if (!jp.parse_object(doc ? doc : (const uint8_t*)"", len, arena, &root)) {
+        *out_len = 0;
+        return GPUDIFF_E_DECODE;
+    }
+    std::string o;
+    update_body(root, mode, rv, rv_len, o);
+    return give(o, out, cap, out_len);
+}
+
+int gpudiff_splice_resource_version(const uint8_t* body, size_t len, uint32_t off, uint32_t form, const uint8_t* rv,
+                                    size_t rv_len, uint8_t* out, size_t cap, size_t* out_len) {
+    constexpr uint32_t kKnown = GPUDIFF_RV_INSERT | GPUDIFF_RV_LEAD | GPUDIFF_RV_TRAIL | GPUDIFF_RV_WRAP;
+    if ((!body && len) || (!rv && rv_len) || !out_len) return GPUDIFF_E_INVAL;
+    if ((form & ~kKnown) || (form != GPUDIFF_RV_NONE && !(form & GPUDIFF_RV_INSERT)) || off > len)
+        return GPUDIFF_E_INVAL;
+    const bool insert = form != GPUDIFF_RV_NONE && rv_len != 0;
+    if (form != GPUDIFF_RV_NONE && (off == 0 || off >= len)) return GPUDIFF_E_INVAL;  // inside the outer braces
+    std::string text;
+    if (insert) {
+        if (form & GPUDIFF_RV_LEAD) text.push_back(',');
+        text += (form & GPUDIFF_RV_WRAP) ? "\"metadata\":{\"resourceVersion\":" : "\"resourceVersion\":";
+        put_go_str(text, rv, rv_len);
+        if (form & GPUDIFF_RV_WRAP) text.push_back('}');
+        if (form & GPUDIFF_RV_TRAIL) text.push_back(',');
+    }
+    *out_len = len + text.size();
+    if (*out_len > cap || (!out && *out_len)) return GPUDIFF_E_CAPACITY;
+    const size_t at = insert ? off : len;
+    if (at) memcpy(out, body, at);
+    if (!text.empty()) memcpy(out + at, text.data(), text.size());
+    if (len > at) memcpy(out + at + text.size(), body + at, len - at);
+    return GPUDIFF_OK;
+}
+
+int gpudiff_bodies_rv_splice(gpudiff_ctx*, const gpudiff_bodies* b, gpudiff_rv_splice* out) {
+    if (!b || !out || !b->internal) return GPUDIFF_E_INVAL;
+    const BodiesStore* bs = (const BodiesStore*)b->internal;
+    if (bs->rv_off.size() != b->n || bs->rv_form.size() != b->n) return GPUDIFF_E_STATE;
+    out->n = b->n;
+    out->off = bs->rv_off.data();
+    out->form = bs->rv_form.data();
+    out->n_device = bs->rv_device;
+    out->n_host = bs->rv_host;
     return GPUDIFF_OK;
 }
 
@@ -445,8 +686,9 @@ int gpudiff_wbatch_fetch(gpudiff_ctx* c, gpudiff_wbatch* wb, gpudiff_bodies* out
         if (to[i].status != GPUDIFF_TOK_OK) def.push_back((uint32_t)i);
     std::vector<std::string> hb(def.size());
     std::vector<uint8_t> hok(def.size(), 0);
+    std::vector<RvSplice> hrv(def.size());
     for_deferred(c, def.size(), [&](size_t k) {
-        hok[k] = host_body(wb->src[def[k]], wb->lens[def[k]], wb->mode, hb[k]) ? 1 : 0;
+        hok[k] = host_body(wb->src[def[k]], wb->lens[def[k]], wb->mode, hb[k], &hrv[k]) ? 1 : 0;
     });
     bs->k10.resize(n);
     uint64_t dev_bytes = 0;
@@ -455,10 +697,10 @@ int gpudiff_wbatch_fetch(gpudiff_ctx* c, gpudiff_wbatch* wb, gpudiff_bodies* out
         bs->k10[i] = (int32_t)to[i].status;
         if (to[i].status != GPUDIFF_TOK_OK) {
             const size_t h = k++;
-            return host_body_of(hb[h], hok[h]);
+            return host_body_of(hb[h], hok[h], hrv[h]);
         }
         dev_bytes += to[i].bytes;
-        return Body{Body::kDevice, raw.data() + to[i].off, to[i].bytes};
+        return device_body_of(raw.data(), to[i]);
     });
     wb->body_bytes = dev_bytes;
     publish(bs, out, n, def.size());
@@ -636,10 +878,11 @@ int gpudiff_write_plan_get_ex(gpudiff_ctx* c, gpudiff_ticket ticket, uint32_t mo
     }
     std::vector<std::string> hb(def.size());
     std::vector<uint8_t> hok(def.size(), 0);
+    std::vector<RvSplice> hrv(def.size());
     const uint32_t mode_split = n_spec_docs;
     for_deferred(c, def.size(), [&](size_t k) {
         hok[k] = host_body(hjson.data() + hoff[k], docs[def[k]].json_len,
-                           def[k] < mode_split ? GPUDIFF_UPSERT_SPEC : GPUDIFF_UPSERT_STATUS, hb[k])
+                           def[k] < mode_split ? GPUDIFF_UPSERT_SPEC : GPUDIFF_UPSERT_STATUS, hb[k], &hrv[k])
                      ? 1
                      : 0;
     });
@@ -652,8 +895,8 @@ int gpudiff_write_plan_get_ex(gpudiff_ctx* c, gpudiff_ticket ticket, uint32_t mo
         if (wdoc[w] == UINT32_MAX) return Body{Body::kNone, nullptr, 0};  // no-op write: no body
         const uint32_t k = wdoc[w];
         bs->k10[w] = (int32_t)to[k].status;
-        if (to[k].status != GPUDIFF_TOK_OK) return host_body_of(hb[hidx[k]], hok[hidx[k]]);
-        return Body{Body::kDevice, raw.data() + to[k].off, to[k].bytes};
+        if (to[k].status != GPUDIFF_TOK_OK) return host_body_of(hb[hidx[k]], hok[hidx[k]], hrv[hidx[k]]);
+        return device_body_of(raw.data(), to[k]);
     });
     publish(bs, &out->bodies, nw, def.size());
     out->n = nw;
@@ -682,8 +925,9 @@ int gpudiff_store_write_plan_get(gpudiff_ctx* c, gpudiff_store* st, gpudiff_tick
     const size_t nw = sp.n, n_def = sp.def.size();
     std::vector<std::string> hb(n_def);
     std::vector<uint8_t> hok(n_def, 0);
+    std::vector<RvSplice> hrv(n_def);
     for_deferred(c, n_def, [&](size_t k) {
-        hok[k] = host_body(sp.hjson.data() + sp.hoff[k], sp.hlen[k], sp.kind[sp.def[k]], hb[k]) ? 1 : 0;
+        hok[k] = host_body(sp.hjson.data() + sp.hoff[k], sp.hlen[k], sp.kind[sp.def[k]], hb[k], &hrv[k]) ? 1 : 0;
     });
     std::unique_ptr<PlanStore> ps(new (std::nothrow) PlanStore());
     std::unique_ptr<BodiesStore> bs(new (std::nothrow) BodiesStore());
@@ -697,14 +941,19 @@ int gpudiff_store_write_plan_get(gpudiff_ctx* c, gpudiff_store* st, gpudiff_tick
         bs->source.assign(nw, GPUDIFF_BODY_DEVICE);
         bs->offsets.assign(sp.offsets, sp.offsets + nw + 1);
         bs->bytes.assign(sp.bytes, sp.bytes + sp.offsets[nw]);
+        bs->rv_off.assign(sp.rv_off, sp.rv_off + nw);  // K19 left a no-op write's descriptor GPUDIFF_RV_NONE
+        bs->rv_form.assign(sp.rv_form, sp.rv_form + nw);
+        for (size_t w = 0; w < nw; w++) bs->rv_device += sp.noop[w] ? 0 : 1;
     } else {  // the host's bodies go in between
         size_t k = 0;
         assemble_bodies(bs.get(), nw, [&](size_t w) {
             if (k < n_def && sp.def[k] == w) {
                 const size_t h = k++;
-                return host_body_of(hb[h], hok[h]);
+                return host_body_of(hb[h], hok[h], hrv[h]);
             }
-            return Body{Body::kDevice, sp.bytes + sp.offsets[w], (size_t)(sp.offsets[w + 1] - sp.offsets[w])};
+            if (sp.noop[w]) return Body{Body::kNone, nullptr, 0, RvSplice{}};
+            return Body{Body::kDevice, sp.bytes + sp.offsets[w], (size_t)(sp.offsets[w + 1] - sp.offsets[w]),
+                        RvSplice{sp.rv_off[w], sp.rv_form[w]}};
         });
     }
     publish(bs.release(), &out->bodies, nw, n_def);

@@ -222,12 +222,19 @@ UPSERT_SPEC, UPSERT_STATUS = 0, 1
 # gpudiff_write_plan_get_ex modes: which writes, rendered from which document of a pair
 PLAN_INFORMER, PLAN_SPEC, PLAN_STATUS, PLAN_UPSTREAM_DOWNSTREAM = 0x0, 0x1, 0x2, 0x4
 BODY_DEVICE, BODY_HOST = 0, 1
+# a body's resourceVersion splice descriptor (GPUDIFF_RV_*)
+RV_NONE, RV_INSERT, RV_LEAD, RV_TRAIL, RV_WRAP = 0x0, 0x1, 0x2, 0x4, 0x8
 
 
 class Bodies(C.Structure):
     _fields_ = [("n", C.c_size_t), ("offsets", C.c_void_p), ("bytes", C.c_void_p), ("status", C.c_void_p),
                 ("source", C.c_void_p), ("k10_status", C.c_void_p), ("n_host", C.c_size_t),
                 ("internal", C.c_void_p)]
+
+
+class RvSpliceC(C.Structure):
+    _fields_ = [("n", C.c_size_t), ("off", C.c_void_p), ("form", C.c_void_p), ("n_device", C.c_size_t),
+                ("n_host", C.c_size_t)]
 
 
 class WritePlanC(C.Structure):
@@ -438,6 +445,14 @@ SIGNATURES = [
     ("gpudiff_wbatch_free", None, [_P, _P]),
     ("gpudiff_upsert_body_host", C.c_int, [C.c_char_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t,
                                            C.POINTER(C.c_size_t)]),
+    ("gpudiff_bodies_rv_splice", C.c_int, [_P, C.POINTER(Bodies), C.POINTER(RvSpliceC)]),
+    ("gpudiff_splice_resource_version", C.c_int, [C.c_char_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_char_p,
+                                                  C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("gpudiff_upsert_body_host_rv", C.c_int, [C.c_char_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t,
+                                              C.POINTER(C.c_size_t), C.POINTER(C.c_uint32),
+                                              C.POINTER(C.c_uint32)]),
+    ("gpudiff_update_body_host", C.c_int, [C.c_char_p, C.c_size_t, C.c_uint32, C.c_char_p, C.c_size_t,
+                                           C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("gpudiff_rbatch_create", C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_size_t,
                                         C.POINTER(_P)]),
     ("gpudiff_rbatch_run", C.c_int, [_P, _P]),
@@ -793,7 +808,7 @@ def _take_write_plan(ctx, wp: WritePlanC) -> "WritePlan":
         return WritePlan(pair_index=_arr(wp.pair_index, n, np.uint32), kind=_arr(wp.kind, n, np.uint8),
                          noop=_arr(wp.noop, n, np.uint8),
                          bodies=[None if st[i] != OK else raw[int(offs[i]):int(offs[i + 1])] for i in range(n)],
-                         source=src, n_host=int(b.n_host))
+                         source=src, n_host=int(b.n_host), rv=_take_rv_splice(ctx, b))
     finally:
         _lib.gpudiff_write_plan_release(ctx, C.byref(wp))
 
@@ -1247,6 +1262,11 @@ class WritePlan:
     bodies: List[Optional[bytes]]  # b"" for no-op writes, None = undecodable
     source: np.ndarray
     n_host: int
+    rv: Optional["RvSplice"] = None
+
+    def rv_splice(self):
+        """(off uint32[n], form uint8[n]): where each body's resourceVersion member goes (RV_*)."""
+        return self.rv.off, self.rv.form
 
 
 @dataclass
@@ -1255,6 +1275,27 @@ class BodyList:
     source: np.ndarray             # BODY_DEVICE / BODY_HOST
     k10_status: np.ndarray         # K10's TOK_* per document
     n_host: int
+    rv: Optional["RvSplice"] = None
+
+    def rv_splice(self):
+        """(off uint32[n], form uint8[n]): where each body's resourceVersion member goes (RV_*)."""
+        return self.rv.off, self.rv.form
+
+
+@dataclass
+class RvSplice:
+    """gpudiff_rv_splice, copied: the descriptors and who computed them (K10 / the host path)."""
+    off: np.ndarray
+    form: np.ndarray
+    n_device: int
+    n_host: int
+
+
+def _take_rv_splice(ctx, b: Bodies) -> RvSplice:
+    """gpudiff_bodies_rv_splice of bodies not yet released, copied."""
+    r = RvSpliceC()
+    _chk(_lib.gpudiff_bodies_rv_splice(ctx, C.byref(b), C.byref(r)), "gpudiff_bodies_rv_splice")
+    return RvSplice(_arr(r.off, r.n, np.uint32), _arr(r.form, r.n, np.uint8), int(r.n_device), int(r.n_host))
 
 
 class WBatch:
@@ -1283,7 +1324,7 @@ class WBatch:
             total = int(offs[-1]) if n else 0
             raw = C.string_at(b.bytes, total) if total else b""
             bodies = [None if st[i] != OK else raw[int(offs[i]):int(offs[i + 1])] for i in range(n)]
-            return BodyList(bodies, src, k10, int(b.n_host))
+            return BodyList(bodies, src, k10, int(b.n_host), _take_rv_splice(self.eng.ctx, b))
         finally:
             _lib.gpudiff_bodies_release(self.eng.ctx, C.byref(b))
 
@@ -1507,6 +1548,47 @@ def upsert_body_host(doc, mode: int = UPSERT_SPEC) -> Optional[bytes]:
     _chk(_lib.gpudiff_upsert_body_host(b, len(b), mode, C.cast(out, C.c_void_p), n.value, C.byref(n)),
          "gpudiff_upsert_body_host")
     return out.raw[:n.value]
+
+
+def _sized_call(name, call) -> Optional[bytes]:
+    """A host-only entry point that writes into (out, cap, out_len): sized by a first call, filled by a second.
+    None on a Go decode error."""
+    n = C.c_size_t()
+    rc = call(None, 0, C.byref(n))
+    if rc == E_DECODE:
+        return None
+    if rc not in (OK, E_CAPACITY):
+        _chk(rc, name)
+    out = C.create_string_buffer(max(1, n.value))
+    _chk(call(C.cast(out, C.c_void_p), n.value, C.byref(n)), name)
+    return out.raw[:n.value]
+
+
+def upsert_body_host_rv(doc, mode: int = UPSERT_SPEC):
+    """The host path's body and its resourceVersion splice point: (body, off, form), or None on a Go decode
+    error."""
+    b = to_json_bytes(doc)
+    off, form = C.c_uint32(), C.c_uint32()
+    body = _sized_call("gpudiff_upsert_body_host_rv", lambda out, cap, n: _lib.gpudiff_upsert_body_host_rv(
+        b, len(b), mode, out, cap, n, C.byref(off), C.byref(form)))
+    return None if body is None else (body, off.value, form.value)
+
+
+def splice_resource_version(body: bytes, off: int, form: int, rv: bytes) -> bytes:
+    """gpudiff_splice_resource_version: the Update body from a rendered body, its descriptor and the live
+    resourceVersion (raw bytes, escaped as Go escapes a string)."""
+    rv = rv.encode() if isinstance(rv, str) else bytes(rv)
+    return _sized_call("gpudiff_splice_resource_version", lambda out, cap, n: _lib.gpudiff_splice_resource_version(
+        body, len(body), off, form, rv, len(rv), out, cap, n))
+
+
+def update_body_host(doc, mode: int, rv: bytes) -> Optional[bytes]:
+    """gpudiff_update_body_host: the Update body marshalled directly (the transform, SetResourceVersion(rv),
+    marshal), or None on a Go decode error."""
+    b = to_json_bytes(doc)
+    rv = rv.encode() if isinstance(rv, str) else bytes(rv)
+    return _sized_call("gpudiff_update_body_host", lambda out, cap, n: _lib.gpudiff_update_body_host(
+        b, len(b), mode, rv, len(rv), out, cap, n))
 
 
 def resolve_path(old, new, path_hash: int, path_kind: int, path_hash_bits: int = PATH_HASH_BITS) -> str:
