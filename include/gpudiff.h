@@ -719,6 +719,10 @@ void gpudiff_bodies_release(gpudiff_ctx* ctx, gpudiff_bodies* b);
 #define GPUDIFF_PLAN_SPEC 0x1u
 #define GPUDIFF_PLAN_STATUS 0x2u
 #define GPUDIFF_PLAN_UPSTREAM_DOWNSTREAM 0x4u
+/* gpudiff_store_write_plan_get: also bring back each body's request target (gpudiff_bodies_targets), 16 B more per
+ * write in the list that comes back.  gpudiff_write_plan_get_ex accepts and ignores it: its bodies always carry
+ * their targets. */
+#define GPUDIFF_PLAN_TARGETS 0x8u
 typedef struct gpudiff_write_plan {
     size_t n;                    /* writes: the spec-dirty pairs (ascending index), then the status-dirty ones */
     const uint32_t* pair_index;  /* the pair's index in the submitted batch */
@@ -752,7 +756,9 @@ void gpudiff_write_plan_release(gpudiff_ctx* ctx, gpudiff_write_plan* p);
  * issue the same write once per event).  The plan of batch b is a function of batch b's events and flags alone: it
  * does not look at batch b + 1, and it does not look at gpudiff_store_forget.
  * mode: GPUDIFF_PLAN_SPEC / GPUDIFF_PLAN_STATUS select the kinds (neither = both);
- * GPUDIFF_PLAN_UPSTREAM_DOWNSTREAM is GPUDIFF_E_INVAL (store events are informer events).
+ * GPUDIFF_PLAN_UPSTREAM_DOWNSTREAM is GPUDIFF_E_INVAL (store events are informer events); GPUDIFF_PLAN_TARGETS adds
+ * each body's request target to the list that comes back (16 B a write; without it the plan's bodies answer
+ * gpudiff_bodies_targets with GPUDIFF_E_STATE and the copy back is what it was).
  * The bodies come from the batch's JSON still staged in HBM: nothing is uploaded again, and only the bodies' bytes
  * come back.  Call after gpudiff_wait on the ticket and before the submit after the next one (which reuses the ring
  * slot); GPUDIFF_E_STATE otherwise, for an unknown or unwaited ticket, for a host-encode store (its JSON never
@@ -855,6 +861,64 @@ int gpudiff_upsert_body_host_rv(const uint8_t* doc, size_t len, uint32_t mode, u
  * descriptor has to do per write.  Results as gpudiff_upsert_body_host. */
 int gpudiff_update_body_host(const uint8_t* doc, size_t len, uint32_t mode, const uint8_t* rv, size_t rv_len,
                              uint8_t* out, size_t cap, size_t* out_len);
+
+/* ---- the request target: the object's namespace and name ----
+ * Controller.process reads meta.GetNamespace(), meta.GetName() first (pkg/syncer/syncer.go:310) and takes from them
+ * the in-syncer-namespace skip (:311, :352-363), ensureNamespaceExists (specsyncer.go:87), getClient(gvr, namespace)
+ * (syncer.go:344-350), the Get(name) before every Update (specsyncer.go:116, statussyncer.go:50) and Delete(name)
+ * (specsyncer.go:83).  With each body the engine reports where those two strings stand in it, so a consumer that
+ * holds only the plan sends the body without decoding it again.
+ *
+ * Two fields per body, GetName() / GetNamespace() = NestedString(obj, "metadata", field).  A field is PRESENT when
+ * the root has a "metadata" member whose value is a JSON object ({} counts; null, a string, a number, a list do
+ * not), that object has a member whose decoded key is exactly the field's name, and that member's value is a JSON
+ * string; otherwise it is absent and its value is "".  The last of duplicate keys wins, as everywhere in Go's decode.
+ *
+ * Canonical, so that two implementations compare byte for byte: an absent field has offset 0, length 0 and no flag;
+ * a present field has its flag, also when the value is "" (length 0, the offset just behind the opening quote);
+ * _ESC is set exactly when the rendered span holds a backslash, i.e. Go's encoder escaped something in it -- without
+ * _ESC the span is the value itself; a write without a body (a no-op, a Go decode error) has all fields zero. */
+#define GPUDIFF_TGT_NAME 0x1u
+#define GPUDIFF_TGT_NAME_ESC 0x2u
+#define GPUDIFF_TGT_NS 0x4u
+#define GPUDIFF_TGT_NS_ESC 0x8u
+typedef struct gpudiff_targets {
+    size_t n;             /* = the bodies' n */
+    const uint32_t* off;  /* 2n: [2i] name, [2i+1] namespace; offset from the body's first byte of the first byte
+                             after the value's opening quote */
+    const uint32_t* len;  /* 2n: rendered bytes up to the closing quote */
+    const uint8_t* flags; /* n: GPUDIFF_TGT_* */
+    size_t n_device;      /* descriptors K10 computed (the bodies it rendered) */
+    size_t n_host;        /* descriptors the host path computed (the bodies it marshalled; not decode errors) */
+} gpudiff_targets;
+/* The descriptors of `b` (of gpudiff_upsert_bodies / gpudiff_wbatch_fetch, or &plan.bodies of either write plan).
+ * The arrays live as long as the bodies do.  GPUDIFF_E_STATE for the bodies of a gpudiff_store_write_plan_get
+ * without GPUDIFF_PLAN_TARGETS. */
+int gpudiff_bodies_targets(gpudiff_ctx* ctx, const gpudiff_bodies* b, gpudiff_targets* out);
+/* body[off, off + len) with JSON escaping undone (what Go's encoder emits: \" \\ \n \r \t \b \f \uXXXX), into
+ * out[0, cap); host only, no context.  *out_len = the result's length, also when it does not fit (then
+ * GPUDIFF_E_CAPACITY).  GPUDIFF_E_INVAL: a span outside the body or a malformed escape. */
+int gpudiff_target_decode(const uint8_t* body, size_t body_len, uint32_t off, uint32_t len, uint8_t* out, size_t cap,
+                          size_t* out_len);
+/* One document decoded and its two NestedString values returned directly: the independent second implementation the
+ * descriptors are tested against, what a Delete event uses (it has no body), and what a caller without the
+ * descriptor has to do per write.  *name_len / *ns_len are set also when a value does not fit (then
+ * GPUDIFF_E_CAPACITY).  GPUDIFF_E_DECODE as gpudiff_upsert_body_host. */
+int gpudiff_target_host(const uint8_t* doc, size_t len, uint8_t* name_out, size_t name_cap, size_t* name_len,
+                        uint8_t* ns_out, size_t ns_cap, size_t* ns_len);
+/* The distinct (cluster_id, namespace) pairs among the writes that have a body (status 0, not empty) and are not
+ * skipped (skip[w] != 0), in order of first appearance: group_of[w] = the write's group, 0xFFFFFFFF for a write that
+ * is not grouped; first[g] = the group's first write; *n_groups = their number.  ensureNamespaceExists then runs once
+ * per namespace and downstream cluster instead of once per write.  cluster_ids (n, may be NULL: one cluster) and
+ * skip (n, may be NULL) are the caller's; group_of and first hold n each.  Keys are compared as rendered bytes --
+ * exact, because Go's encoding of a string is canonical; an absent namespace and "" fall into the same group. */
+int gpudiff_targets_namespaces(const gpudiff_bodies* bodies, const gpudiff_targets* targets,
+                               const uint32_t* cluster_ids, const uint8_t* skip, uint32_t* group_of, uint32_t* first,
+                               size_t* n_groups);
+/* gpudiff_upsert_body_host plus the body's target descriptor as the host path records it while it writes the body:
+ * off[2], len[2] ([0] name, [1] namespace) and *flags. */
+int gpudiff_upsert_body_host_targets(const uint8_t* doc, size_t len, uint32_t mode, uint8_t* out, size_t cap,
+                                     size_t* out_len, uint32_t* off, uint32_t* tlen, uint32_t* flags);
 
 /* ---- Deployment splitter status roll-up ----
  * pkg/reconciler/deployment/deployment.go:41-91: when a leaf Deployment

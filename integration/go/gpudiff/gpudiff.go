@@ -1118,6 +1118,11 @@ type Write struct {
 	// where the live resourceVersion goes for client.Update / UpdateStatus: SpliceRV(Body, RVOff, RVForm, rv)
 	RVOff  uint32
 	RVForm uint8
+	// the request target, meta.GetName() / meta.GetNamespace() of the object the body renders (syncer.go:310), read
+	// from the body by its descriptor (gpudiff_bodies_targets) with no decode; "" when absent, as NestedString
+	// gives it.  A store plan carries them only when asked with PlanTargets.
+	Name      string
+	Namespace string
 }
 
 // Plan modes (GPUDIFF_PLAN_*): which writes DiffAndPlanMode lists and which document they render.
@@ -1126,6 +1131,7 @@ const (
 	PlanSpec               = uint32(C.GPUDIFF_PLAN_SPEC)                // only spec writes (an upstream informer's batch)
 	PlanStatus             = uint32(C.GPUDIFF_PLAN_STATUS)              // only status writes (a downstream informer's batch)
 	PlanUpstreamDownstream = uint32(C.GPUDIFF_PLAN_UPSTREAM_DOWNSTREAM) // pairs are (A upstream, B downstream)
+	PlanTargets            = uint32(C.GPUDIFF_PLAN_TARGETS)             // Store.WritePlan: fill Write.Name / Namespace
 )
 
 // DiffAndPlan is DiffAndPlanMode(olds, news, PlanInformer).
@@ -1199,6 +1205,14 @@ func writesOf(plan *C.gpudiff_write_plan) []Write {
 		ro = (*[1 << 30]C.uint32_t)(unsafe.Pointer(rv.off))[:m:m]
 		rf = (*[1 << 30]C.uint8_t)(unsafe.Pointer(rv.form))[:m:m]
 	}
+	var tg C.gpudiff_targets
+	var to, tl []C.uint32_t
+	var tf []C.uint8_t
+	if C.gpudiff_bodies_targets(nil, &plan.bodies, &tg) == C.GPUDIFF_OK { // E_STATE: a store plan without PlanTargets
+		to = (*[1 << 30]C.uint32_t)(unsafe.Pointer(tg.off))[: 2*m : 2*m]
+		tl = (*[1 << 30]C.uint32_t)(unsafe.Pointer(tg.len))[: 2*m : 2*m]
+		tf = (*[1 << 30]C.uint8_t)(unsafe.Pointer(tg.flags))[:m:m]
+	}
 	for k := 0; k < m; k++ {
 		w := Write{Pair: int(idx[k]), Kind: Mode(kind[k]), Noop: noop[k] != 0}
 		if !w.Noop && st[k] == 0 {
@@ -1207,16 +1221,72 @@ func writesOf(plan *C.gpudiff_write_plan) []Write {
 			if ro != nil {
 				w.RVOff, w.RVForm = uint32(ro[k]), uint8(rf[k])
 			}
+			if tf != nil {
+				w.Name = targetString(w.Body, uint32(to[2*k]), uint32(tl[2*k]), uint8(tf[k])&TgtNameEsc != 0)
+				w.Namespace = targetString(w.Body, uint32(to[2*k+1]), uint32(tl[2*k+1]), uint8(tf[k])&TgtNsEsc != 0)
+			}
 		}
 		writes[k] = w
 	}
 	return writes
 }
 
+// The flags of a request target descriptor (GPUDIFF_TGT_*).
+const (
+	TgtName    = uint8(C.GPUDIFF_TGT_NAME)     // metadata.name is present (a string)
+	TgtNameEsc = uint8(C.GPUDIFF_TGT_NAME_ESC) // its rendered span holds an escape
+	TgtNs      = uint8(C.GPUDIFF_TGT_NS)       // metadata.namespace is present
+	TgtNsEsc   = uint8(C.GPUDIFF_TGT_NS_ESC)
+)
+
+// targetString is body[off, off+n) as the string it renders: the bytes themselves, or -- when the encoder escaped
+// something in the span -- encoding/json's reading of them between their quotes.  A span that does not fit the body
+// (not the engine's) gives "".
+// NOT COMPILED HERE, like the rest of this shim.
+func targetString(body []byte, off, n uint32, esc bool) string {
+	if n == 0 || off == 0 || uint64(off)+uint64(n) >= uint64(len(body)) {
+		return ""
+	}
+	if !esc {
+		return string(body[off : off+n])
+	}
+	var s string
+	if json.Unmarshal(body[off-1:off+n+1], &s) != nil {
+		return ""
+	}
+	return s
+}
+
+// TargetHost decodes one document and returns its (namespace, name) directly (gpudiff_target_host): what a Delete
+// event uses, since it has no body, and what a consumer without the descriptor has to do per write.  ok is false when
+// Go cannot decode the document.
+// NOT COMPILED HERE, like the rest of this shim.
+func TargetHost(doc []byte) (namespace, name string, ok bool) {
+	p, l := cmem(doc)
+	defer C.free(unsafe.Pointer(p))
+	capN, capS := C.size_t(256), C.size_t(256)
+	for {
+		nb, sb := C.malloc(capN), C.malloc(capS)
+		var nn, sn C.size_t
+		rc := C.gpudiff_target_host(p, l, (*C.uint8_t)(nb), capN, &nn, (*C.uint8_t)(sb), capS, &sn)
+		if rc == C.GPUDIFF_OK {
+			name, namespace = C.GoStringN((*C.char)(nb), C.int(nn)), C.GoStringN((*C.char)(sb), C.int(sn))
+		}
+		C.free(nb)
+		C.free(sb)
+		if rc == C.GPUDIFF_E_CAPACITY {
+			capN, capS = nn+1, sn+1
+			continue
+		}
+		return namespace, name, rc == C.GPUDIFF_OK
+	}
+}
+
 // WritePlan lists the writes of one waited batch of a device-encode store (gpudiff_store_write_plan_get): one
 // write per dirty slot and kind, rendering the slot's LAST version of the batch from the JSON still staged in HBM
 // -- the worker re-reads the latest object from the indexer (syncer.go:318), and the store is that indexer.
 // Write.Pair is that event's index in the submitted batch.  mode: PlanSpec / PlanStatus select the kinds (0: both);
+// PlanTargets fills Write.Name / Write.Namespace (16 B more per write come back);
 // PlanUpstreamDownstream is refused (store events are informer events).  Call after the ticket was waited and
 // before the submit after the next one reuses its ring slot.
 func (s *Store) WritePlan(ticket uint64, mode uint32) ([]Write, error) {

@@ -1685,13 +1685,15 @@ int grow_plan(T** p, uint64_t* cap, uint64_t need) {
 }
 
 // the write list as K18 / K19 write it and one copy brings it back: 8-B words, then 4-B, then bytes
+// (the targets, when asked for, among the 4-B words)
 struct PlanHead {
-    uint64_t off_pair, off_src, off_k10, off_kind, off_noop, bytes;
-    explicit PlanHead(uint64_t nw) {
+    uint64_t off_pair, off_src, off_k10, off_tgt, off_kind, off_noop, bytes;
+    PlanHead(uint64_t nw, bool targets) {
         off_pair = 8 * (nw + 1);
         off_src = off_pair + 4 * nw;
         off_k10 = off_src + 4 * nw;
-        off_kind = off_k10 + 4 * nw;
+        off_tgt = off_k10 + 4 * nw;
+        off_kind = off_tgt + (targets ? sizeof(TargetWords) * nw : 0);
         off_noop = off_kind + nw;
         bytes = (off_noop + nw + 7) & ~7ull;
     }
@@ -1703,7 +1705,7 @@ struct PlanHead {
 // pass's flags on R.d -- and writes only the slot's pl_* buffers, so it runs on the readback stream: never behind
 // the other batch in flight on the kernel stream.  Its last read of djson / dmeta is marked in R.k0_done, which
 // the slot's next upload waits for (lifetimes).
-int dstore_write_plan(gpudiff_ctx* c, DStore* s, gpudiff_ticket t, uint32_t kinds, StorePlan* out) {
+int dstore_write_plan(gpudiff_ctx* c, DStore* s, gpudiff_ticket t, uint32_t kinds, bool targets, StorePlan* out) {
     if (!s || s->broken || s->pair_mode || !t) return GPUDIFF_E_STATE;
     Ring* Rp = nullptr;
     for (Ring& Q : s->ring)
@@ -1749,13 +1751,14 @@ int dstore_write_plan(gpudiff_ctx* c, DStore* s, gpudiff_ticket t, uint32_t kind
                    n_td = rec[kColStatusDocs], ndocs = n_sd + n_td;
     if (nw > 2ull * nd || ndocs > nw) return GPUDIFF_E_DEVICE;  // not a scan of this table
     out->n = (size_t)nw;
-    const PlanHead H(nw);
+    const PlanHead H(nw, targets);
     auto map_words = [&]() {
         const uint8_t* b = (const uint8_t*)out->words.data();
         out->offsets = out->words.data();
         out->pair_index = (const uint32_t*)(b + H.off_pair);
         out->src_doc = (const uint32_t*)(b + H.off_src);
         out->k10 = (const int32_t*)(b + H.off_k10);
+        out->tgt = targets ? (const TargetWords*)(b + H.off_tgt) : nullptr;
         out->kind = b + H.off_kind;
         out->noop = b + H.off_noop;
         out->bytes = b + H.bytes;
@@ -1788,7 +1791,8 @@ int dstore_write_plan(gpudiff_ctx* c, DStore* s, gpudiff_ticket t, uint32_t kind
     if (timing) HIPCHK(hipEventRecord(R.pl_ev[3], st));
     if (timing) HIPCHK(hipEventRecord(R.pl_ev[4], st));
     HIPCHK(launch_body_lens(st, R.pl_wdoc, R.pl_touts, (uint32_t)nw, (uint32_t)ndocs, R.pl_lens,
-                            (uint32_t*)(R.pl_head + H.off_k10), R.pl_tiles, R.pl_rec + 8));
+                            (uint32_t*)(R.pl_head + H.off_k10),
+                            targets ? (TargetWords*)(R.pl_head + H.off_tgt) : nullptr, R.pl_tiles, R.pl_rec + 8));
     uint64_t total = 0;
     HIPCHK(hipMemcpyAsync(&total, R.pl_rec + 8, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));

@@ -41,7 +41,8 @@ int dstore_staged_mark_read(gpudiff_ctx* c, gpudiff_ticket t);
 // the host (gathered on the device, one copy back).  upsert.cpp marshals those and wraps the result.
 struct StorePlan {
     size_t n = 0;                  // writes
-    // offsets[n + 1] | pair_index[n] | src_doc[n] | k10[n] | kind[n] | noop[n] | pad | bytes; k10[] comes back as
+    // offsets[n + 1] | pair_index[n] | src_doc[n] | k10[n] | tgt[n] (16 B each, only when asked for) | kind[n] |
+    // noop[n] | pad | bytes; k10[] comes back as
     // K10's verdict words (store_plan.h plan_k10_word) and is unpacked in place, the splice points into rv_*_v
     std::vector<uint64_t> words;
     const uint64_t* offsets = nullptr;    // dense: body w = bytes[offsets[w], offsets[w + 1]); empty unless K10 rendered it
@@ -52,6 +53,8 @@ struct StorePlan {
     const uint8_t* noop = nullptr;
     const uint32_t* rv_off = nullptr;     // K10's resourceVersion splice point per write (GPUDIFF_RV_*; a write
     const uint8_t* rv_form = nullptr;     // without a device body: 0 / GPUDIFF_RV_NONE)
+    const gd::TargetWords* tgt = nullptr; // K10's request target per write (all zero without a device body); null
+                                          // unless the plan was asked for targets
     const uint8_t* bytes = nullptr;
     std::vector<uint32_t> rv_off_v;
     std::vector<uint8_t> rv_form_v;
@@ -60,9 +63,9 @@ struct StorePlan {
     std::vector<uint64_t> hoff;
     std::vector<uint32_t> hlen;
 };
-// kinds: GPUDIFF_PLAN_SPEC | GPUDIFF_PLAN_STATUS.  GPUDIFF_E_STATE: not a waited ticket of this store whose ring slot
+// kinds: GPUDIFF_PLAN_SPEC | GPUDIFF_PLAN_STATUS; targets: GPUDIFF_PLAN_TARGETS was asked for.  GPUDIFF_E_STATE: not a waited ticket of this store whose ring slot
 // still holds the batch, or the store is broken; GPUDIFF_E_CAPACITY: no device memory for the plan's buffers
-int dstore_write_plan(gpudiff_ctx* c, DStore* s, gpudiff_ticket t, uint32_t kinds, StorePlan* out);
+int dstore_write_plan(gpudiff_ctx* c, DStore* s, gpudiff_ticket t, uint32_t kinds, bool targets, StorePlan* out);
 int dstore_plan_stats(const DStore* s, gpudiff_store_plan_stats* out);
 // store.cpp: the device-encode store behind a gpudiff_store, null for a host-encode one
 DStore* gpudiff_store_dstore(gpudiff_store* s);

@@ -27,6 +27,7 @@
 //   M8 value offsets top-down by depth, visibility
 //   M8b the byte offset at which the Update body's `"resourceVersion":"<rv>"` goes, and its commas (marks from M2,
 //      ends gathered by M9, settled after it)
+//   M8c the request target: where metadata.name's and metadata.namespace's values stand in the body (nodes from M2)
 //   M9 emit: every visible node writes its comma, key and value text
 // Anything outside this subset keeps a nonzero status and the host marshals
 // the document (upsert.cpp, the Go-exact path).
@@ -192,8 +193,9 @@ __device__ __forceinline__ void marshal_m1_floats(const DocTree& T, const Marsha
 // ---------------------------------------------------------- M2-M4 transform marks, child lists, owner references
 // mmode: GPUDIFF_UPSERT_* (owner references are normalized in spec mode only)
 // Returns whether the root has a "metadata" member that is no object (the Update body then takes no splice).
+// name_node / ns_node: metadata's "name" / "namespace" member when its value is a string, else NONE (M8c).
 __device__ __forceinline__ bool marshal_m2_m4_children(const DocTree& T, const MarshalScratch& M, uint32_t mmode,
-                                                       uint32_t& status) {
+                                                       uint32_t& status, uint32_t& name_node, uint32_t& ns_node) {
     const uint8_t* const d = T.d;
     const uint32_t lane = T.lane, nn = T.nn, meta_node = T.meta_node, labels_node = T.labels_node;
     const bool labels_ok = T.labels_ok;
@@ -201,8 +203,10 @@ __device__ __forceinline__ bool marshal_m2_m4_children(const DocTree& T, const M
     // ---------------------------------------------------------- M2 transform marks, child counts
     uint32_t orf = NONE, owned = NONE;
     bool meta_other = false;
+    name_node = NONE;
+    ns_node = NONE;
     if (status == GPUDIFF_TOK_OK) {
-        uint32_t my_orf = NONE, my_owned = NONE;
+        uint32_t my_orf = NONE, my_owned = NONE, my_name = NONE, my_ns = NONE;
         bool my_meta_other = false;
         for (uint32_t i0 = 1; i0 < nn; i0 += 64) {
             const uint32_t i = i0 + lane;
@@ -216,6 +220,10 @@ __device__ __forceinline__ bool marshal_m2_m4_children(const DocTree& T, const M
                 } else {
                     if (mmode == GPUDIFF_UPSERT_SPEC && field_fold(K, "ownerReferences", 15) == 1u) my_orf = i;
                     if (key_win_cmp(K, "resourceVersion", 15) < 0) M.fl[i] |= MF_RVPRE;  // for M9's splice point
+                    if (r.w & NI_STR) {  // NestedString: a string value, the key byte for byte
+                        if (field_fold(K, "name", 4) == 1u) my_name = i;
+                        else if (field_fold(K, "namespace", 9) == 1u) my_ns = i;
+                    }
                 }
             } else if (meta_node == NONE && r.x == 0u) {
                 // no metadata object: the splice wraps the member into a "metadata" member of the root -- unless
@@ -231,6 +239,8 @@ __device__ __forceinline__ bool marshal_m2_m4_children(const DocTree& T, const M
         // duplicate keys are resolved (deferred) by M5 before anything is emitted
         orf = wave_min_v(my_orf);
         owned = wave_min_v(my_owned);
+        name_node = wave_min_v(my_name);
+        ns_node = wave_min_v(my_ns);
         if (meta_node == NONE) meta_other = ballot(my_meta_other) != 0;
     }
     wave_sync();
@@ -566,6 +576,27 @@ __device__ __forceinline__ void marshal_m8b_rv_splice(const DocTree& T, const Ma
     }
 }
 
+// ---------------------------------------------------------- M8c the request target
+// Where the values of metadata.name and metadata.namespace stand in the body (include/gpudiff.h GPUDIFF_TGT_*): M2
+// found the two members among metadata's (the key window it compares anyway; a duplicate key defers the document in
+// M5), M1 knows whether each string renders as its own bytes, M8 placed the value.  A string's text is its quotes
+// around the rendered bytes, so the span is [vst + 1, vst + sz - 1).  Three words of each node, read once.
+static_assert(GPUDIFF_TGT_NS == GPUDIFF_TGT_NAME << 2 && GPUDIFF_TGT_NS_ESC == GPUDIFF_TGT_NAME_ESC << 2,
+              "the namespace's flags are the name's, two bits up");
+__device__ __forceinline__ void marshal_m8c_targets(const MarshalScratch& M, uint32_t name_node, uint32_t ns_node,
+                                                    TokOut& o) {
+    uint32_t off[2] = {0, 0}, len[2] = {0, 0}, flags = 0;
+    const uint32_t node[2] = {name_node, ns_node};
+#pragma unroll
+    for (uint32_t k = 0; k < 2; k++) {
+        if (node[k] == NONE) continue;
+        off[k] = M.vst[node[k]] + 1u;
+        len[k] = M.sz[node[k]] - 2u;
+        flags |= (GPUDIFF_TGT_NAME | ((M.fl[node[k]] & MF_VCLEAN) ? 0u : GPUDIFF_TGT_NAME_ESC)) << (2u * k);
+    }
+    tokout_set_targets(o, off[0], len[0], off[1], len[1], flags);
+}
+
 // ---------------------------------------------------------- M9 emit
 // dst: the body's place; sz0, any_float: from M6-M8 and M1.  Returns this lane's part of M8b: the largest end of a
 // visible MF_RVPRE member's value it wrote (0: none).
@@ -725,7 +756,8 @@ __device__ __forceinline__ void marshal_doc(const DocTree& T, uint8_t* work, uin
     mark(PM_M1);
     if (status == GPUDIFF_TOK_OK && any_float) marshal_m1_floats(T, M);
     mark(PM_M1_FLOATS);
-    const bool meta_other = marshal_m2_m4_children(T, M, mmode, status);
+    uint32_t name_node, ns_node;
+    const bool meta_other = marshal_m2_m4_children(T, M, mmode, status, name_node, ns_node);
     mark(PM_M2_M4);
     marshal_m5_ranks(T, M, status);
     mark(PM_M5);
@@ -737,6 +769,7 @@ __device__ __forceinline__ void marshal_doc(const DocTree& T, uint8_t* work, uin
         uint32_t rv_off, rv_form;
         marshal_m8b_rv_splice(T, M, meta_other, rv_end, rv_off, rv_form);
         tokout_set_rv_splice(o, rv_off, rv_form);
+        marshal_m8c_targets(M, name_node, ns_node, o);
     }
     o.n_nodes = T.nn;
     o.status = status;

@@ -58,9 +58,11 @@ hipError_t launch_plan_docs(hipStream_t s, const PlanIn& in, const uint8_t* word
                             const uint64_t* rec, const PlanLists& out);
 // per write, the bytes K10 rendered for it (0: a no-op write, or a document K10 left to the host) and K10's verdict
 // word (store_plan.h plan_k10_word: a status that leaves the body to the host, else the body's resourceVersion splice
-// point -- body-relative, so packing keeps it); tile sums of the lengths; rec[0] = their total
+// point -- body-relative, so packing keeps it); tile sums of the lengths; rec[0] = their total.  tgt (or null:
+// not asked for): per write, the body's request target words (tokenize.h TargetWords), body-relative too
 hipError_t launch_body_lens(hipStream_t s, const uint32_t* wdoc, const TokOut* touts, uint32_t n_writes,
-                            uint32_t n_docs, uint64_t* lens, uint32_t* k10, uint64_t* tiles, uint64_t* rec);
+                            uint32_t n_docs, uint64_t* lens, uint32_t* k10, TargetWords* tgt, uint64_t* tiles,
+                            uint64_t* rec);
 // offsets[n_writes + 1] (dense, byte-exact) + K19: body w from its arena slot to bytes[offsets[w], offsets[w + 1])
 hipError_t launch_pack_bodies(hipStream_t s, const uint32_t* wdoc, const TokOut* touts, uint32_t n_writes,
                               uint32_t n_docs, const uint64_t* lens, const uint64_t* tiles, uint64_t* offsets,

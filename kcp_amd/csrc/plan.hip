@@ -14,7 +14,8 @@
 //   K18 k_plan_docs      the same tile prefix again, plus the tile's base: each write into the write list, each body
 //                        into K10's TokDoc table -- document order is event order, so each kind comes out ascending
 //   k_body_lens          K10's output sizes per write, then scanned (scan64.h: sums, top, offsets); with them K10's
-//                        status and resourceVersion splice point, through the same wdoc indirection
+//                        status and resourceVersion splice point, through the same wdoc indirection -- and, for a
+//                        plan with GPUDIFF_PLAN_TARGETS, the body's request target (four words of the same TokOut)
 //   K19 k_pack_bodies    wave per body: from its arena slot (2 x len + 512 B apart) to its byte-exact dense offset
 //
 // K19's copy works at dword granularity (store_plan.h plan_copy_body): a dense offset has any alignment, so each
@@ -159,12 +160,13 @@ __global__ __launch_bounds__(kPlanTile) void k_plan_docs(const PlanIn in, const 
 // ---------------------------------------------------------------- K19
 __global__ __launch_bounds__(256) void k_body_lens(const uint32_t* __restrict__ wdoc, const TokOut* __restrict__ touts,
                                                    uint32_t n_writes, uint32_t n_docs, uint64_t* __restrict__ lens,
-                                                   uint32_t* __restrict__ k10) {
+                                                   uint32_t* __restrict__ k10, TargetWords* __restrict__ tgt) {
     const uint32_t w = blockIdx.x * blockDim.x + threadIdx.x;
     if (w >= n_writes) return;
     const uint32_t d = wdoc[w];
     uint64_t len = 0;
     uint32_t st = GPUDIFF_TOK_OK, ro = 0, rf = GPUDIFF_RV_NONE;
+    TargetWords tw{};  // a no-op write, a body left to the host: all zero
     if (d < n_docs) {  // kPlanNoDoc: a no-op write
         const TokOut t = touts[d];
         st = t.status;
@@ -172,9 +174,11 @@ __global__ __launch_bounds__(256) void k_body_lens(const uint32_t* __restrict__ 
             len = t.bytes;
             ro = tokout_rv_off(t);
             rf = tokout_rv_form(t);
+            tw = tokout_targets(t);
         }
     }
     lens[w] = len;
+    if (tgt) tgt[w] = tw;
     k10[w] = plan_k10_word(st, ro, rf);
 }
 
@@ -225,9 +229,10 @@ hipError_t launch_plan_docs(hipStream_t s, const PlanIn& in, const uint8_t* word
 }
 
 hipError_t launch_body_lens(hipStream_t s, const uint32_t* wdoc, const TokOut* touts, uint32_t n_writes,
-                            uint32_t n_docs, uint64_t* lens, uint32_t* k10, uint64_t* tiles, uint64_t* rec) {
+                            uint32_t n_docs, uint64_t* lens, uint32_t* k10, TargetWords* tgt, uint64_t* tiles,
+                            uint64_t* rec) {
     if (!n_writes) return hipMemsetAsync(rec, 0, 8, s);
-    k_body_lens<<<(n_writes + 255) / 256, 256, 0, s>>>(wdoc, touts, n_writes, n_docs, lens, k10);
+    k_body_lens<<<(n_writes + 255) / 256, 256, 0, s>>>(wdoc, touts, n_writes, n_docs, lens, k10, tgt);
     return launch_scan64_sums(s, lens, n_writes, tiles, rec);
 }
 

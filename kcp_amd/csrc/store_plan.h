@@ -70,6 +70,7 @@ constexpr uint32_t kPlanRvBit = 1u << 31, kPlanRvFormShift = 26, kPlanRvOffMask 
 static_assert(2ull * kTokMaxLen + 512u + 15u <= kPlanRvOffMask, "an offset inside marshal_out_cap(len) fits 26 bits");
 static_assert(((GPUDIFF_RV_INSERT | GPUDIFF_RV_LEAD | GPUDIFF_RV_TRAIL | GPUDIFF_RV_WRAP) << kPlanRvFormShift) <
                   kPlanRvBit, "the form fits below bit 31");
+static_assert(kTgtFlagShift == kPlanRvFormShift, "a target offset (tokenize.h TargetWords) fits the same 26 bits");
 __host__ __device__ inline uint32_t plan_k10_word(uint32_t status, uint32_t rv_off, uint32_t rv_form) {
     return status != GPUDIFF_TOK_OK ? status & ~kPlanRvBit
                                     : kPlanRvBit | (rv_form << kPlanRvFormShift) | (rv_off & kPlanRvOffMask);

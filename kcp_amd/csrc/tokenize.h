@@ -59,6 +59,29 @@ __host__ __device__ inline void tokout_set_rv_splice(TokOut& o, uint32_t off, ui
 }
 __host__ __device__ inline uint32_t tokout_rv_off(const TokOut& o) { return o.spec_l; }
 __host__ __device__ inline uint32_t tokout_rv_form(const TokOut& o) { return o.spec_ar; }
+// ... and the body's request target (include/gpudiff.h GPUDIFF_TGT_*) in the other four: stat_l = metadata.name's
+// offset in bits 0-25 (an offset inside marshal_out_cap(len) fits them: store_plan.h) with the flags in bits 26-29,
+// stat_ar = its length, oflags = metadata.namespace's offset, n_tab = its length.  All 0 unless status is
+// GPUDIFF_TOK_OK.  The same four words are a write's targets in the store plan's list (plan.hip k_body_lens).
+struct TargetWords {
+    uint32_t w[4];
+};
+constexpr uint32_t kTgtFlagShift = 26, kTgtOffMask = (1u << kTgtFlagShift) - 1u;
+__host__ __device__ inline void tokout_set_targets(TokOut& o, uint32_t name_off, uint32_t name_len, uint32_t ns_off,
+                                                   uint32_t ns_len, uint32_t flags) {
+    o.stat_l = (name_off & kTgtOffMask) | (flags << kTgtFlagShift);
+    o.stat_ar = name_len;
+    o.oflags = ns_off;
+    o.n_tab = ns_len;
+}
+__host__ __device__ inline TargetWords tokout_targets(const TokOut& o) {
+    return TargetWords{{o.stat_l, o.stat_ar, o.oflags, o.n_tab}};
+}
+__host__ __device__ inline uint32_t target_name_off(const TargetWords& t) { return t.w[0] & kTgtOffMask; }
+__host__ __device__ inline uint32_t target_name_len(const TargetWords& t) { return t.w[1]; }
+__host__ __device__ inline uint32_t target_ns_off(const TargetWords& t) { return t.w[2]; }
+__host__ __device__ inline uint32_t target_ns_len(const TargetWords& t) { return t.w[3]; }
+__host__ __device__ inline uint32_t target_flags(const TargetWords& t) { return t.w[0] >> kTgtFlagShift; }
 
 __host__ __device__ inline uint64_t tok_align(uint64_t x) { return (x + 255u) & ~(uint64_t)255u; }
 __host__ __device__ inline uint32_t tok_cap(uint32_t len) { return len + 2u; }

@@ -22,6 +22,7 @@
 #include <charconv>
 #include <string>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 
 #include "doc_batch.h"
@@ -37,6 +38,12 @@ namespace gd {
 struct RvSplice {
     uint32_t off = 0;
     uint32_t form = GPUDIFF_RV_NONE;
+};
+// a body's request target (include/gpudiff.h GPUDIFF_TGT_*): [0] metadata.name, [1] metadata.namespace
+struct Targets {
+    uint32_t off[2] = {0, 0};
+    uint32_t len[2] = {0, 0};
+    uint32_t flags = 0;
 };
 }  // namespace gd
 
@@ -350,8 +357,9 @@ void put_go_str(std::string& o, const uint8_t* s, size_t n) {
 
 namespace gd {
 
-// The body for one decoded object (root: a J_OBJ); *sp (optional) = where its resourceVersion member would go.
-void upsert_body(const Node& root, uint32_t mode, std::string& o, RvSplice* sp) {
+// The body for one decoded object (root: a J_OBJ); *sp (optional) = where its resourceVersion member would go, *tg
+// (optional) = where metadata.name's and metadata.namespace's values stand in it.
+void upsert_body(const Node& root, uint32_t mode, std::string& o, RvSplice* sp, Targets* tg) {
     o.clear();
     const Member* md = find(root, "metadata");
     const bool md_map = md && md->v.t == J_OBJ;
@@ -360,6 +368,7 @@ void upsert_body(const Node& root, uint32_t mode, std::string& o, RvSplice* sp) 
     size_t owned_len = 0;
     if (md_map && mode == GPUDIFF_UPSERT_SPEC) owned_by(md->v, &owned, &owned_len);
     SplicePoint root_pt, meta_pt;
+    Targets tgt;
     o.push_back('{');
     root_pt.open = o.size();
     bool first = true;
@@ -386,7 +395,17 @@ void upsert_body(const Node& root, uint32_t mode, std::string& o, RvSplice* sp) 
             if (mode == GPUDIFF_UPSERT_SPEC && is("ownerReferences")) {
                 if (!put_owner_refs(item, x->v, owned, owned_len)) continue;
             } else {
+                // NestedString(obj, "metadata", field): the decoded key byte for byte (the parser kept the last of
+                // duplicates), a string value
+                const int k = x->v.t != J_STR ? -1 : is("name") ? 0 : is("namespace") ? 1 : -1;
+                const size_t vs = item.size();
                 put_value(item, x->v);
+                if (k >= 0) {
+                    tgt.off[k] = (uint32_t)(o.size() + vs + 1);
+                    tgt.len[k] = (uint32_t)(item.size() - vs - 2);
+                    const bool esc = memchr(item.data() + vs + 1, '\\', tgt.len[k]) != nullptr;
+                    tgt.flags |= (GPUDIFF_TGT_NAME | (esc ? GPUDIFF_TGT_NAME_ESC : 0u)) << (2 * k);
+                }
             }
             o += item;
             f2 = false;
@@ -397,6 +416,23 @@ void upsert_body(const Node& root, uint32_t mode, std::string& o, RvSplice* sp) 
     o.push_back('}');
     o.push_back('\n');
     if (sp) *sp = md_map ? meta_pt.done(0) : md ? RvSplice{} : root_pt.done(GPUDIFF_RV_WRAP);
+    if (tg) *tg = tgt;
+}
+
+// Unstructured.GetName() / GetNamespace(): NestedString(obj, "metadata", field) on the decoded object, "" unless the
+// whole path is there and ends in a string
+void target_strings(const Node& root, const char** p, size_t* n) {
+    static const char* const kField[2] = {"name", "namespace"};
+    const Member* md = find(root, "metadata");
+    for (int k = 0; k < 2; k++) {
+        p[k] = "";
+        n[k] = 0;
+        if (!md || md->v.t != J_OBJ) continue;
+        const Member* f = find(md->v, kField[k]);
+        if (!f || f->v.t != J_STR) continue;
+        p[k] = f->v.u.s;
+        n[k] = f->v.n;
+    }
 }
 
 // The Update body for one decoded object: the transform of `mode`, then SetResourceVersion(rv) =
@@ -405,7 +441,7 @@ void upsert_body(const Node& root, uint32_t mode, std::string& o, RvSplice* sp) 
 void update_body(const Node& root, uint32_t mode, const uint8_t* rv, size_t rv_len, std::string& o) {
     const Member* md = find(root, "metadata");
     if (!rv_len || (md && md->v.t != J_OBJ)) {  // RemoveNestedField; SetNestedField's error, dropped
-        upsert_body(root, mode, o, nullptr);
+        upsert_body(root, mode, o, nullptr, nullptr);
         return;
     }
     struct Item {
@@ -477,7 +513,36 @@ struct BodiesStore {
     std::vector<uint32_t> rv_off;
     std::vector<uint8_t> rv_form;
     size_t rv_device = 0, rv_host = 0;
+    // per body, its request target (gpudiff_bodies_targets): off / len hold [2w] name, [2w + 1] namespace.  Not
+    // there (has_tgt false) for a store plan that was not asked for them
+    std::vector<uint32_t> tgt_off, tgt_len;
+    std::vector<uint8_t> tgt_flags;
+    bool has_tgt = false;
+    void set_targets(size_t w, const Targets& t) {
+        for (int k = 0; k < 2; k++) {
+            tgt_off[2 * w + k] = t.off[k];
+            tgt_len[2 * w + k] = t.len[k];
+        }
+        tgt_flags[w] = (uint8_t)t.flags;
+    }
+    void clear_targets(size_t nw) {
+        tgt_off.assign(2 * nw, 0);
+        tgt_len.assign(2 * nw, 0);
+        tgt_flags.assign(nw, 0);
+        has_tgt = true;
+    }
 };
+
+// K10's target words (tokenize.h TargetWords: a TokOut's, or a store plan write's)
+Targets targets_of(const TargetWords& g) {
+    Targets t;
+    t.off[0] = target_name_off(g);
+    t.len[0] = target_name_len(g);
+    t.off[1] = target_ns_off(g);
+    t.len[1] = target_ns_len(g);
+    t.flags = target_flags(g);
+    return t;
+}
 
 void publish(BodiesStore* bs, gpudiff_bodies* out, size_t n, size_t n_host) {
     out->n = n;
@@ -497,17 +562,20 @@ struct Body {
     const uint8_t* p;
     size_t n;
     RvSplice rv;  // of a kDevice / kHost body: K10's (TokOut) or the host marshaller's
+    Targets tgt;  // likewise
 };
 
 // offsets / bytes / status / source of bs for nw writes.  body_of(w) is called exactly once per write, for
 // w = 0, 1, ..., nw - 1 in that order: the callers' lambdas count deferred writes and fill bs->k10 as they go
+// targets: the bodies carry their request targets (always, but for a store plan that was not asked for them)
 template <class F>
-void assemble_bodies(BodiesStore* bs, size_t nw, F&& body_of) {
+void assemble_bodies(BodiesStore* bs, size_t nw, F&& body_of, bool targets = true) {
     bs->offsets.resize(nw + 1);
     bs->status.assign(nw, 0);
     bs->source.assign(nw, GPUDIFF_BODY_DEVICE);
     bs->rv_off.assign(nw, 0);
     bs->rv_form.assign(nw, GPUDIFF_RV_NONE);
+    if (targets) bs->clear_targets(nw);
     for (size_t w = 0; w < nw; w++) {
         bs->offsets[w] = bs->bytes.size();
         const Body b = body_of(w);
@@ -518,29 +586,35 @@ void assemble_bodies(BodiesStore* bs, size_t nw, F&& body_of) {
             bs->rv_off[w] = b.rv.off;
             bs->rv_form[w] = (uint8_t)b.rv.form;
             (b.kind == Body::kDevice ? bs->rv_device : bs->rv_host)++;
+            if (targets) bs->set_targets(w, b.tgt);
         }
     }
     bs->offsets[nw] = bs->bytes.size();
 }
 
 // the host path's answer for one deferred write
-Body host_body_of(const std::string& body, bool ok, const RvSplice& rv) {
-    return ok ? Body{Body::kHost, (const uint8_t*)body.data(), body.size(), rv}
-              : Body{Body::kDecodeError, nullptr, 0, RvSplice{}};
+struct HostDesc {
+    RvSplice rv;
+    Targets tgt;
+};
+Body host_body_of(const std::string& body, bool ok, const HostDesc& d) {
+    return ok ? Body{Body::kHost, (const uint8_t*)body.data(), body.size(), d.rv, d.tgt}
+              : Body{Body::kDecodeError, nullptr, 0, RvSplice{}, Targets{}};
 }
 
-// K10's answer for one write: the body's bytes in `raw` and the descriptor in its TokOut
+// K10's answer for one write: the body's bytes in `raw` and the descriptors in its TokOut
 Body device_body_of(const uint8_t* raw, const TokOut& t) {
-    return Body{Body::kDevice, raw + t.off, t.bytes, RvSplice{tokout_rv_off(t), tokout_rv_form(t)}};
+    return Body{Body::kDevice, raw + t.off, t.bytes, RvSplice{tokout_rv_off(t), tokout_rv_form(t)},
+                targets_of(tokout_targets(t))};
 }
 
-// host marshal of one document into o, its splice point into *rv; false = Go decode error
-bool host_body(const uint8_t* doc, size_t len, uint32_t mode, std::string& o, RvSplice* rv) {
+// host marshal of one document into o, its descriptors into *d; false = Go decode error
+bool host_body(const uint8_t* doc, size_t len, uint32_t mode, std::string& o, HostDesc* d) {
     JsonParser jp;
     Arena arena;
     Node root;
     if (!jp.parse_object(doc, len, arena, &root)) return false;
-    upsert_body(root, mode, o, rv);
+    upsert_body(root, mode, o, &d->rv, &d->tgt);
     return true;
 }
 
@@ -562,19 +636,172 @@ int gpudiff_upsert_body_host(const uint8_t* doc, size_t len, uint32_t mode, uint
     return gpudiff_upsert_body_host_rv(doc, len, mode, out, cap, out_len, &off, &form);
 }
 
+int gpudiff_upsert_body_host_targets(const uint8_t* doc, size_t len, uint32_t mode, uint8_t* out, size_t cap,
+                                     size_t* out_len, uint32_t* off, uint32_t* tlen, uint32_t* flags) {
+    if ((!doc && len) || !out_len || !off || !tlen || !flags || mode > GPUDIFF_UPSERT_STATUS) return GPUDIFF_E_INVAL;
+    std::string o;
+    HostDesc d;
+    off[0] = off[1] = tlen[0] = tlen[1] = *flags = 0;
+    if (!host_body(doc ? doc : (const uint8_t*)"", len, mode, o, &d)) {
+        *out_len = 0;
+        return GPUDIFF_E_DECODE;
+    }
+    for (int k = 0; k < 2; k++) {
+        off[k] = d.tgt.off[k];
+        tlen[k] = d.tgt.len[k];
+    }
+    *flags = d.tgt.flags;
+    return give(o, out, cap, out_len);
+}
+
+int gpudiff_target_host(const uint8_t* doc, size_t len, uint8_t* name_out, size_t name_cap, size_t* name_len,
+                        uint8_t* ns_out, size_t ns_cap, size_t* ns_len) {
+    if ((!doc && len) || !name_len || !ns_len) return GPUDIFF_E_INVAL;
+    *name_len = *ns_len = 0;
+    JsonParser jp;
+    Arena arena;
+    Node root;
+    if (!jp.parse_object(doc ? doc : (const uint8_t*)"", len, arena, &root)) return GPUDIFF_E_DECODE;
+    const char* p[2];
+    size_t n[2];
+    target_strings(root, p, n);
+    *name_len = n[0];
+    *ns_len = n[1];
+    if (n[0] > name_cap || n[1] > ns_cap || (!name_out && n[0]) || (!ns_out && n[1])) return GPUDIFF_E_CAPACITY;
+    if (n[0]) memcpy(name_out, p[0], n[0]);
+    if (n[1]) memcpy(ns_out, p[1], n[1]);
+    return GPUDIFF_OK;
+}
+
+int gpudiff_target_decode(const uint8_t* body, size_t body_len, uint32_t off, uint32_t len, uint8_t* out, size_t cap,
+                          size_t* out_len) {
+    if ((!body && body_len) || !out_len) return GPUDIFF_E_INVAL;
+    *out_len = 0;
+    if ((uint64_t)off + len > body_len) return GPUDIFF_E_INVAL;
+    const uint8_t* const s = body + off;
+    auto hex4 = [&](size_t i, uint32_t* v) {  // s[i, i + 4) as a code unit
+        if (i + 4 > len) return false;
+        *v = 0;
+        for (size_t k = 0; k < 4; k++) {
+            const uint8_t c = s[i + k];
+            const uint32_t d = c >= '0' && c <= '9' ? c - '0' : c >= 'a' && c <= 'f' ? c - 'a' + 10u
+                               : c >= 'A' && c <= 'F' ? c - 'A' + 10u : 16u;
+            if (d > 15u) return false;
+            *v = *v << 4 | d;
+        }
+        return true;
+    };
+    size_t w = 0;
+    auto put = [&](uint8_t c) {
+        if (out && w < cap) out[w] = c;
+        w++;
+    };
+    for (size_t i = 0; i < len;) {
+        const uint8_t c = s[i++];
+        if (c != '\\') {
+            put(c);
+            continue;
+        }
+        if (i >= len) return GPUDIFF_E_INVAL;
+        const uint8_t e = s[i++];
+        switch (e) {
+            case '"': put('"'); break;
+            case '\\': put('\\'); break;
+            case 'n': put('\n'); break;
+            case 'r': put('\r'); break;
+            case 't': put('\t'); break;
+            case 'b': put('\b'); break;
+            case 'f': put('\f'); break;
+            case 'u': {
+                uint32_t r, lo;
+                if (!hex4(i, &r)) return GPUDIFF_E_INVAL;
+                i += 4;
+                if (r >= 0xD800u && r < 0xDC00u && i + 6 <= len && s[i] == '\\' && s[i + 1] == 'u' && hex4(i + 2, &lo) &&
+                    lo >= 0xDC00u && lo < 0xE000u) {
+                    r = 0x10000u + ((r - 0xD800u) << 10) + (lo - 0xDC00u);
+                    i += 6;
+                } else if (r >= 0xD800u && r < 0xE000u) {
+                    r = 0xFFFDu;  // a lone surrogate, as Go's decoder reads it
+                }
+                if (r < 0x80u) {
+                    put((uint8_t)r);
+                } else if (r < 0x800u) {
+                    put((uint8_t)(0xC0u | r >> 6));
+                    put((uint8_t)(0x80u | (r & 63u)));
+                } else if (r < 0x10000u) {
+                    put((uint8_t)(0xE0u | r >> 12));
+                    put((uint8_t)(0x80u | ((r >> 6) & 63u)));
+                    put((uint8_t)(0x80u | (r & 63u)));
+                } else {
+                    put((uint8_t)(0xF0u | r >> 18));
+                    put((uint8_t)(0x80u | ((r >> 12) & 63u)));
+                    put((uint8_t)(0x80u | ((r >> 6) & 63u)));
+                    put((uint8_t)(0x80u | (r & 63u)));
+                }
+                break;
+            }
+            default: return GPUDIFF_E_INVAL;
+        }
+    }
+    *out_len = w;
+    return (w > cap || (!out && w)) ? GPUDIFF_E_CAPACITY : GPUDIFF_OK;
+}
+
+int gpudiff_targets_namespaces(const gpudiff_bodies* b, const gpudiff_targets* t, const uint32_t* cluster_ids,
+                               const uint8_t* skip, uint32_t* group_of, uint32_t* first, size_t* n_groups) {
+    if (!b || !t || !n_groups || t->n != b->n || b->n > 0xFFFFFFFEull) return GPUDIFF_E_INVAL;
+    const size_t n = b->n;
+    *n_groups = 0;
+    if (n && (!group_of || !first || !b->offsets || !b->status || !t->off || !t->len)) return GPUDIFF_E_INVAL;
+    std::unordered_map<std::string, uint32_t> groups;
+    std::string key;
+    try {
+        for (size_t w = 0; w < n; w++) {
+            group_of[w] = 0xFFFFFFFFu;
+            const uint64_t bo = b->offsets[w], bl = b->offsets[w + 1] - bo;
+            if ((skip && skip[w]) || b->status[w] != 0 || bl == 0) continue;
+            const uint32_t off = t->off[2 * w + 1], len = t->len[2 * w + 1];
+            if ((uint64_t)off + len > bl) return GPUDIFF_E_INVAL;
+            const uint32_t cl = cluster_ids ? cluster_ids[w] : 0u;
+            key.assign((const char*)&cl, sizeof(cl));  // absent and "": both an empty span
+            key.append((const char*)b->bytes + bo + off, len);
+            const auto it = groups.emplace(key, (uint32_t)groups.size());
+            if (it.second) first[it.first->second] = (uint32_t)w;
+            group_of[w] = it.first->second;
+        }
+    } catch (const std::bad_alloc&) {
+        return GPUDIFF_E_NOMEM;
+    }
+    *n_groups = groups.size();
+    return GPUDIFF_OK;
+}
+
+int gpudiff_bodies_targets(gpudiff_ctx*, const gpudiff_bodies* b, gpudiff_targets* out) {
+    if (!b || !out || !b->internal) return GPUDIFF_E_INVAL;
+    const BodiesStore* bs = (const BodiesStore*)b->internal;
+    if (!bs->has_tgt || bs->tgt_flags.size() != b->n) return GPUDIFF_E_STATE;
+    out->n = b->n;
+    out->off = bs->tgt_off.data();
+    out->len = bs->tgt_len.data();
+    out->flags = bs->tgt_flags.data();
+    out->n_device = bs->rv_device;  // the same bodies carry both descriptors
+    out->n_host = bs->rv_host;
+    return GPUDIFF_OK;
+}
+
 int gpudiff_upsert_body_host_rv(const uint8_t* doc, size_t len, uint32_t mode, uint8_t* out, size_t cap,
                                 size_t* out_len, uint32_t* off, uint32_t* form) {
     if ((!doc && len) || !out_len || !off || !form || mode > GPUDIFF_UPSERT_STATUS) return GPUDIFF_E_INVAL;
     std::string o;
-    RvSplice rv;
+    HostDesc d;
     *off = 0;
     *form = GPUDIFF_RV_NONE;
-    if (!host_body(doc ? doc : (const uint8_t*)"", len, mode, o, &rv)) {
+    if (!host_body(doc ? doc : (const uint8_t*)"", len, mode, o, &d)) {
         *out_len = 0;
         return GPUDIFF_E_DECODE;
     }
-    *off = rv.off;
-    *form = rv.form;
+    *off = d.rv.off;
+    *form = d.rv.form;
     return give(o, out, cap, out_len);
 }
 
@@ -686,7 +913,7 @@ int gpudiff_wbatch_fetch(gpudiff_ctx* c, gpudiff_wbatch* wb, gpudiff_bodies* out
         if (to[i].status != GPUDIFF_TOK_OK) def.push_back((uint32_t)i);
     std::vector<std::string> hb(def.size());
     std::vector<uint8_t> hok(def.size(), 0);
-    std::vector<RvSplice> hrv(def.size());
+    std::vector<HostDesc> hrv(def.size());
     for_deferred(c, def.size(), [&](size_t k) {
         hok[k] = host_body(wb->src[def[k]], wb->lens[def[k]], wb->mode, hb[k], &hrv[k]) ? 1 : 0;
     });
@@ -757,7 +984,9 @@ int gpudiff_write_plan_get(gpudiff_ctx* c, gpudiff_ticket ticket, gpudiff_write_
 
 int gpudiff_write_plan_get_ex(gpudiff_ctx* c, gpudiff_ticket ticket, uint32_t mode, gpudiff_write_plan* out) {
     if (!c || !out) return GPUDIFF_E_INVAL;
-    if (mode & ~(GPUDIFF_PLAN_SPEC | GPUDIFF_PLAN_STATUS | GPUDIFF_PLAN_UPSTREAM_DOWNSTREAM)) return GPUDIFF_E_INVAL;
+    if (mode & ~(GPUDIFF_PLAN_SPEC | GPUDIFF_PLAN_STATUS | GPUDIFF_PLAN_UPSTREAM_DOWNSTREAM | GPUDIFF_PLAN_TARGETS))
+        return GPUDIFF_E_INVAL;
+    mode &= ~GPUDIFF_PLAN_TARGETS;  // the TokOuts come back whole here: the bodies always carry their targets
     const uint32_t kinds = (mode & (GPUDIFF_PLAN_SPEC | GPUDIFF_PLAN_STATUS)) ? mode : (GPUDIFF_PLAN_SPEC | GPUDIFF_PLAN_STATUS);
     // informer pairs (old, new): UpdateFunc enqueues newObj and the worker writes it (specsyncer.go:47-50 ->
     // :86-132, statussyncer.go:32-35 -> :41-63), so both kinds render document 2i+1; (A, B) pairs: the spec
@@ -878,7 +1107,7 @@ int gpudiff_write_plan_get_ex(gpudiff_ctx* c, gpudiff_ticket ticket, uint32_t mo
     }
     std::vector<std::string> hb(def.size());
     std::vector<uint8_t> hok(def.size(), 0);
-    std::vector<RvSplice> hrv(def.size());
+    std::vector<HostDesc> hrv(def.size());
     const uint32_t mode_split = n_spec_docs;
     for_deferred(c, def.size(), [&](size_t k) {
         hok[k] = host_body(hjson.data() + hoff[k], docs[def[k]].json_len,
@@ -892,7 +1121,7 @@ int gpudiff_write_plan_get_ex(gpudiff_ctx* c, gpudiff_ticket ticket, uint32_t mo
     if (!bs) return GPUDIFF_E_NOMEM;
     bs->k10.assign(nw, GPUDIFF_TOK_OK);
     assemble_bodies(bs, nw, [&](size_t w) {
-        if (wdoc[w] == UINT32_MAX) return Body{Body::kNone, nullptr, 0};  // no-op write: no body
+        if (wdoc[w] == UINT32_MAX) return Body{Body::kNone, nullptr, 0, RvSplice{}, Targets{}};  // no-op: no body
         const uint32_t k = wdoc[w];
         bs->k10[w] = (int32_t)to[k].status;
         if (to[k].status != GPUDIFF_TOK_OK) return host_body_of(hb[hidx[k]], hok[hidx[k]], hrv[hidx[k]]);
@@ -913,7 +1142,9 @@ int gpudiff_store_write_plan_get(gpudiff_ctx* c, gpudiff_store* st, gpudiff_tick
                                  gpudiff_write_plan* out) {
     if (!c || !st || !out) return GPUDIFF_E_INVAL;
     // store events are informer events: there is no (A, B) reading of them
-    if (mode & ~(GPUDIFF_PLAN_SPEC | GPUDIFF_PLAN_STATUS)) return GPUDIFF_E_INVAL;
+    if (mode & ~(GPUDIFF_PLAN_SPEC | GPUDIFF_PLAN_STATUS | GPUDIFF_PLAN_TARGETS)) return GPUDIFF_E_INVAL;
+    const bool targets = (mode & GPUDIFF_PLAN_TARGETS) != 0;
+    mode &= ~GPUDIFF_PLAN_TARGETS;
     const uint32_t kinds = mode ? mode : (GPUDIFF_PLAN_SPEC | GPUDIFF_PLAN_STATUS);
     memset(out, 0, sizeof(*out));
     int rc = set_device(c);
@@ -921,11 +1152,11 @@ int gpudiff_store_write_plan_get(gpudiff_ctx* c, gpudiff_store* st, gpudiff_tick
     DStore* ds = gpudiff_store_dstore(st);
     if (!ds) return GPUDIFF_E_STATE;  // a host-encode store: its JSON never reaches HBM
     StorePlan sp;
-    if ((rc = dstore_write_plan(c, ds, ticket, kinds, &sp))) return rc;
+    if ((rc = dstore_write_plan(c, ds, ticket, kinds, targets, &sp))) return rc;
     const size_t nw = sp.n, n_def = sp.def.size();
     std::vector<std::string> hb(n_def);
     std::vector<uint8_t> hok(n_def, 0);
-    std::vector<RvSplice> hrv(n_def);
+    std::vector<HostDesc> hrv(n_def);
     for_deferred(c, n_def, [&](size_t k) {
         hok[k] = host_body(sp.hjson.data() + sp.hoff[k], sp.hlen[k], sp.kind[sp.def[k]], hb[k], &hrv[k]) ? 1 : 0;
     });
@@ -944,6 +1175,10 @@ int gpudiff_store_write_plan_get(gpudiff_ctx* c, gpudiff_store* st, gpudiff_tick
         bs->rv_off.assign(sp.rv_off, sp.rv_off + nw);  // K19 left a no-op write's descriptor GPUDIFF_RV_NONE
         bs->rv_form.assign(sp.rv_form, sp.rv_form + nw);
         for (size_t w = 0; w < nw; w++) bs->rv_device += sp.noop[w] ? 0 : 1;
+        if (targets) {
+            bs->clear_targets(nw);
+            for (size_t w = 0; w < nw; w++) bs->set_targets(w, targets_of(sp.tgt[w]));  // a no-op write's: zero
+        }
     } else {  // the host's bodies go in between
         size_t k = 0;
         assemble_bodies(bs.get(), nw, [&](size_t w) {
@@ -951,10 +1186,10 @@ int gpudiff_store_write_plan_get(gpudiff_ctx* c, gpudiff_store* st, gpudiff_tick
                 const size_t h = k++;
                 return host_body_of(hb[h], hok[h], hrv[h]);
             }
-            if (sp.noop[w]) return Body{Body::kNone, nullptr, 0, RvSplice{}};
+            if (sp.noop[w]) return Body{Body::kNone, nullptr, 0, RvSplice{}, Targets{}};
             return Body{Body::kDevice, sp.bytes + sp.offsets[w], (size_t)(sp.offsets[w + 1] - sp.offsets[w]),
-                        RvSplice{sp.rv_off[w], sp.rv_form[w]}};
-        });
+                        RvSplice{sp.rv_off[w], sp.rv_form[w]}, targets ? targets_of(sp.tgt[w]) : Targets{}};
+        }, targets);
     }
     publish(bs.release(), &out->bodies, nw, n_def);
     out->n = nw;

@@ -221,9 +221,13 @@ ROLLUP_NONE, ROLLUP_DECODE = -1, -2
 UPSERT_SPEC, UPSERT_STATUS = 0, 1
 # gpudiff_write_plan_get_ex modes: which writes, rendered from which document of a pair
 PLAN_INFORMER, PLAN_SPEC, PLAN_STATUS, PLAN_UPSTREAM_DOWNSTREAM = 0x0, 0x1, 0x2, 0x4
+# ObjectStore.write_plan: also bring back each body's request target (16 B more per write)
+PLAN_TARGETS = 0x8
 BODY_DEVICE, BODY_HOST = 0, 1
 # a body's resourceVersion splice descriptor (GPUDIFF_RV_*)
 RV_NONE, RV_INSERT, RV_LEAD, RV_TRAIL, RV_WRAP = 0x0, 0x1, 0x2, 0x4, 0x8
+# a body's request target descriptor (GPUDIFF_TGT_*)
+TGT_NAME, TGT_NAME_ESC, TGT_NS, TGT_NS_ESC = 0x1, 0x2, 0x4, 0x8
 
 
 class Bodies(C.Structure):
@@ -235,6 +239,11 @@ class Bodies(C.Structure):
 class RvSpliceC(C.Structure):
     _fields_ = [("n", C.c_size_t), ("off", C.c_void_p), ("form", C.c_void_p), ("n_device", C.c_size_t),
                 ("n_host", C.c_size_t)]
+
+
+class TargetsC(C.Structure):
+    _fields_ = [("n", C.c_size_t), ("off", C.c_void_p), ("len", C.c_void_p), ("flags", C.c_void_p),
+                ("n_device", C.c_size_t), ("n_host", C.c_size_t)]
 
 
 class WritePlanC(C.Structure):
@@ -453,6 +462,16 @@ SIGNATURES = [
                                               C.POINTER(C.c_uint32)]),
     ("gpudiff_update_body_host", C.c_int, [C.c_char_p, C.c_size_t, C.c_uint32, C.c_char_p, C.c_size_t,
                                            C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("gpudiff_bodies_targets", C.c_int, [_P, C.POINTER(Bodies), C.POINTER(TargetsC)]),
+    ("gpudiff_target_decode", C.c_int, [C.c_char_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
+                                        C.POINTER(C.c_size_t)]),
+    ("gpudiff_target_host", C.c_int, [C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
+                                      C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("gpudiff_targets_namespaces", C.c_int, [C.POINTER(Bodies), C.POINTER(TargetsC), C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t)]),
+    ("gpudiff_upsert_body_host_targets", C.c_int, [C.c_char_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t,
+                                                   C.POINTER(C.c_size_t), C.POINTER(C.c_uint32),
+                                                   C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("gpudiff_rbatch_create", C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_size_t,
                                         C.POINTER(_P)]),
     ("gpudiff_rbatch_run", C.c_int, [_P, _P]),
@@ -808,7 +827,7 @@ def _take_write_plan(ctx, wp: WritePlanC) -> "WritePlan":
         return WritePlan(pair_index=_arr(wp.pair_index, n, np.uint32), kind=_arr(wp.kind, n, np.uint8),
                          noop=_arr(wp.noop, n, np.uint8),
                          bodies=[None if st[i] != OK else raw[int(offs[i]):int(offs[i + 1])] for i in range(n)],
-                         source=src, n_host=int(b.n_host), rv=_take_rv_splice(ctx, b))
+                         source=src, n_host=int(b.n_host), rv=_take_rv_splice(ctx, b), tgt=_take_targets(ctx, b))
     finally:
         _lib.gpudiff_write_plan_release(ctx, C.byref(wp))
 
@@ -1263,10 +1282,26 @@ class WritePlan:
     source: np.ndarray
     n_host: int
     rv: Optional["RvSplice"] = None
+    tgt: Optional["Targets"] = None  # None: a store plan that was not asked for them (PLAN_TARGETS)
 
     def rv_splice(self):
         """(off uint32[n], form uint8[n]): where each body's resourceVersion member goes (RV_*)."""
         return self.rv.off, self.rv.form
+
+    def targets(self) -> "Targets":
+        """Each body's request target (gpudiff_bodies_targets); E_STATE for a store plan without PLAN_TARGETS."""
+        if self.tgt is None:
+            raise GpuDiffError(E_STATE, "gpudiff_bodies_targets")
+        return self.tgt
+
+    def namespaces(self, kind: Optional[int] = None, cluster_ids=None, skip=None):
+        """gpudiff_targets_namespaces over the plan's writes: (group_of uint32[n], first uint32[n_groups]), the
+        distinct (cluster, namespace) pairs in order of first appearance; 0xFFFFFFFF = not grouped.  kind
+        (UPSERT_SPEC / UPSERT_STATUS): only the writes of that kind; skip: a further mask."""
+        mask = np.zeros(len(self.bodies), dtype=np.uint8) if skip is None else (np.asarray(skip) != 0).astype(np.uint8)
+        if kind is not None:
+            mask = mask | (self.kind != kind).astype(np.uint8)
+        return targets_namespaces(self.bodies, self.targets(), cluster_ids, mask)
 
 
 @dataclass
@@ -1276,10 +1311,72 @@ class BodyList:
     k10_status: np.ndarray         # K10's TOK_* per document
     n_host: int
     rv: Optional["RvSplice"] = None
+    tgt: Optional["Targets"] = None
 
     def rv_splice(self):
         """(off uint32[n], form uint8[n]): where each body's resourceVersion member goes (RV_*)."""
         return self.rv.off, self.rv.form
+
+    def targets(self) -> "Targets":
+        """Each body's request target (gpudiff_bodies_targets)."""
+        return self.tgt
+
+
+@dataclass
+class Targets:
+    """gpudiff_targets, copied: per body, where metadata.name's ([:, 0]) and metadata.namespace's ([:, 1]) values
+    stand in it, and who computed the descriptors (K10 / the host path)."""
+    off: np.ndarray    # uint32 [n, 2]
+    len: np.ndarray    # uint32 [n, 2]
+    flags: np.ndarray  # uint8 [n]: TGT_*
+    n_device: int
+    n_host: int
+
+    def of(self, bodies, i: int):
+        """(namespace, name) of body i as bytes: the spans, decoded where the encoder escaped something."""
+        out = []
+        for k, esc in ((1, TGT_NS_ESC), (0, TGT_NAME_ESC)):
+            o, n = int(self.off[i, k]), int(self.len[i, k])
+            out.append(target_decode(bodies[i], o, n) if self.flags[i] & esc else (bodies[i][o:o + n] if n else b""))
+        return tuple(out)
+
+
+def _take_targets(ctx, b: Bodies) -> Optional[Targets]:
+    """gpudiff_bodies_targets of bodies not yet released, copied; None when these bodies carry none (E_STATE)."""
+    t = TargetsC()
+    rc = _lib.gpudiff_bodies_targets(ctx, C.byref(b), C.byref(t))
+    if rc == E_STATE:
+        return None
+    _chk(rc, "gpudiff_bodies_targets")
+    n = int(t.n)
+    return Targets(_arr(t.off, 2 * n, np.uint32).reshape(n, 2), _arr(t.len, 2 * n, np.uint32).reshape(n, 2),
+                   _arr(t.flags, n, np.uint8), int(t.n_device), int(t.n_host))
+
+
+def targets_namespaces(bodies, tgt: Targets, cluster_ids=None, skip=None):
+    """gpudiff_targets_namespaces over copied bodies (None = undecodable, b"" = no body) and their targets:
+    (group_of uint32[n], first uint32[n_groups])."""
+    n = len(bodies)
+    offs = np.zeros(n + 1, dtype=np.uint64)
+    offs[1:] = np.cumsum([len(x) if x else 0 for x in bodies], dtype=np.uint64)
+    raw = b"".join(x for x in bodies if x)
+    st = np.array([E_DECODE if x is None else OK for x in bodies], dtype=np.int32)
+    off = np.ascontiguousarray(tgt.off, dtype=np.uint32).reshape(-1)
+    ln = np.ascontiguousarray(tgt.len, dtype=np.uint32).reshape(-1)
+    fl = np.ascontiguousarray(tgt.flags, dtype=np.uint8)
+    b = Bodies(n=n, offsets=offs.ctypes.data, bytes=C.cast(C.c_char_p(raw), C.c_void_p), status=st.ctypes.data)
+    t = TargetsC(n=n, off=off.ctypes.data, len=ln.ctypes.data, flags=fl.ctypes.data)
+    cl = None if cluster_ids is None else np.ascontiguousarray(cluster_ids, dtype=np.uint32)
+    sk = None if skip is None else np.ascontiguousarray(skip, dtype=np.uint8)
+    if (cl is not None and cl.shape != (n,)) or (sk is not None and sk.shape != (n,)):
+        raise GpuDiffError(E_INVAL, "gpudiff_targets_namespaces")
+    group_of = np.zeros(n, dtype=np.uint32)
+    first = np.zeros(n, dtype=np.uint32)
+    ng = C.c_size_t()
+    _chk(_lib.gpudiff_targets_namespaces(C.byref(b), C.byref(t), cl.ctypes.data if cl is not None else None,
+                                         sk.ctypes.data if sk is not None else None, group_of.ctypes.data,
+                                         first.ctypes.data, C.byref(ng)), "gpudiff_targets_namespaces")
+    return group_of, first[:ng.value].copy()
 
 
 @dataclass
@@ -1324,7 +1421,8 @@ class WBatch:
             total = int(offs[-1]) if n else 0
             raw = C.string_at(b.bytes, total) if total else b""
             bodies = [None if st[i] != OK else raw[int(offs[i]):int(offs[i + 1])] for i in range(n)]
-            return BodyList(bodies, src, k10, int(b.n_host), _take_rv_splice(self.eng.ctx, b))
+            return BodyList(bodies, src, k10, int(b.n_host), _take_rv_splice(self.eng.ctx, b),
+                            _take_targets(self.eng.ctx, b))
         finally:
             _lib.gpudiff_bodies_release(self.eng.ctx, C.byref(b))
 
@@ -1572,6 +1670,43 @@ def upsert_body_host_rv(doc, mode: int = UPSERT_SPEC):
     body = _sized_call("gpudiff_upsert_body_host_rv", lambda out, cap, n: _lib.gpudiff_upsert_body_host_rv(
         b, len(b), mode, out, cap, n, C.byref(off), C.byref(form)))
     return None if body is None else (body, off.value, form.value)
+
+
+def upsert_body_host_targets(doc, mode: int = UPSERT_SPEC):
+    """The host path's body and its request target: (body, off[2], len[2], flags) with [0] name, [1] namespace,
+    or None on a Go decode error."""
+    b = to_json_bytes(doc)
+    off, ln, fl = (C.c_uint32 * 2)(), (C.c_uint32 * 2)(), C.c_uint32()
+    body = _sized_call("gpudiff_upsert_body_host_targets", lambda out, cap, n: _lib.gpudiff_upsert_body_host_targets(
+        b, len(b), mode, out, cap, n, off, ln, C.byref(fl)))
+    return None if body is None else (body, (off[0], off[1]), (ln[0], ln[1]), fl.value)
+
+
+def target_decode(body: bytes, off: int, length: int) -> bytes:
+    """gpudiff_target_decode: body[off:off + length] with JSON escaping undone."""
+    out = C.create_string_buffer(max(1, length))  # unescaping never grows a span
+    n = C.c_size_t()
+    _chk(_lib.gpudiff_target_decode(body, len(body), off, length, C.cast(out, C.c_void_p), length, C.byref(n)),
+         "gpudiff_target_decode")
+    return out.raw[:n.value]
+
+
+def target_host(doc, cap: int = 256):
+    """gpudiff_target_host: (namespace, name) of one document as bytes, decoded on the host; None on a Go decode
+    error."""
+    b = to_json_bytes(doc)
+    nn, sn = C.c_size_t(), C.c_size_t()
+    while True:
+        name, ns = C.create_string_buffer(cap), C.create_string_buffer(cap)
+        rc = _lib.gpudiff_target_host(b, len(b), C.cast(name, C.c_void_p), cap, C.byref(nn), C.cast(ns, C.c_void_p),
+                                      cap, C.byref(sn))
+        if rc == E_DECODE:
+            return None
+        if rc == E_CAPACITY:
+            cap = max(nn.value, sn.value, 1)
+            continue
+        _chk(rc, "gpudiff_target_host")
+        return ns.raw[:sn.value], name.raw[:nn.value]
 
 
 def splice_resource_version(body: bytes, off: int, form: int, rv: bytes) -> bytes:
