@@ -15,14 +15,14 @@ CSRC = os.path.join(HERE, "csrc")
 
 SOURCES = ["kernels.hip", "tokenize.hip", "rollup.hip", "negotiate.hip", "dstore.hip", "paths.hip", "plan.hip",
            "scan64.hip", "smallpass.hip", "values.hip", "fanout.hip", "fanout_live.hip", "api.cpp", "fanout.cpp", "store.cpp", "dstore.cpp",
-           "devenc.cpp", "doc_batch.cpp", "upsert.cpp", "rollup.cpp", "negotiate.cpp", "encoder.cpp", "json.cpp",
+           "devenc.cpp", "doc_batch.cpp", "upsert.cpp", "go_marshal.cpp", "rollup.cpp", "negotiate.cpp", "encoder.cpp", "json.cpp",
            "buildid.cpp"]
 SYNTH_SOURCES = ["synth.cpp", "encoder.cpp", "json.cpp", "buildid.cpp"]
 HEADERS = ["kernels.h", "pool.h", "tokenize.h", "tokdev.h", "marshal_phases.h", "rollup_phases.h",
            "negotiate_phases.h", "goscan.h", "rollup.h", "ryu_tables.h", "dstore.h", "dstore_plan.h", "doc_batch.h",
            "decfloat.h", "pow10_128.h", "encoder.h", "engine.h", "json.h", "xxh64.h", "pathstr.h", "stream_paths.h", "plan.h",
            "store_plan.h", "scan64.h", "wave_dev.h", "join_dev.h", "small_pass.h", "values.h", "valstr.h", "fanout.h",
-           "fanout_dev.h"]
+           "fanout_dev.h", "go_marshal.h"]
 MAPS = ["gpudiff.map", "synth.map"]
 INCLUDE_NAMES = ["gpudiff.h", "gpudiff_format.h", "gpudiff_synth.h"]
 INCLUDES = [os.path.join(ROOT, "include", h) for h in INCLUDE_NAMES]

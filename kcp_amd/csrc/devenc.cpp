@@ -6,15 +6,12 @@
 #include <vector>
 
 #include "engine.h"
+#include "go_marshal.h"
 #include "pathstr.h"
 #include "tokenize.h"
 #include "valstr.h"
 
 using namespace gd;
-
-namespace gd {
-uint32_t go_float_text(double f, char* out);  // upsert.cpp: the write path's Go-exact float formatter
-}
 
 namespace {
 

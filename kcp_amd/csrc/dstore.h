@@ -38,7 +38,7 @@ int dstore_staged_mark_read(gpudiff_ctx* c, gpudiff_ticket t);
 // ------------------------------------------------------------------ the store's write plan
 // gpudiff_store_write_plan_get's device side for a waited batch of a device-encode store: the write list and the
 // bodies K10 rendered, as they came back from the device in one allocation, and the JSON of the documents K10 left to
-// the host (gathered on the device, one copy back).  upsert.cpp marshals those and wraps the result.
+// the host (gathered on the device, one copy back).  upsert.cpp has go_marshal.cpp marshal those and wraps the result.
 struct StorePlan {
     size_t n = 0;                  // writes
     // offsets[n + 1] | pair_index[n] | src_doc[n] | k10[n] | tgt[n] (16 B each, only when asked for) | kind[n] |

@@ -30,7 +30,7 @@
 //   M8c the request target: where metadata.name's and metadata.namespace's values stand in the body (nodes from M2)
 //   M9 emit: every visible node writes its comma, key and value text
 // Anything outside this subset keeps a nonzero status and the host marshals
-// the document (upsert.cpp, the Go-exact path).
+// the document (go_marshal.cpp, the Go-exact path).
 #pragma once
 #include "tokdev.h"
 

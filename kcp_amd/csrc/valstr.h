@@ -5,7 +5,7 @@
 // compiles it alone.
 //
 // The text is what the write path's encoder puts on the wire for the leaf
-// (json.NewEncoder(w).Encode, restated by upsert.cpp and K10), rendered from
+// (json.NewEncoder(w).Encode, restated by go_marshal.cpp and K10), rendered from
 // the canonical value the blob stores: the literals, int64 digits, Go's
 // shortest float64 form, and a string as '"' + HTML-safe escaping + '"'.
 //
@@ -20,7 +20,7 @@
 //
 // The float digits are the caller's: fmt(bits, out) returns the length of Go's
 // text of the float64 `bits` and writes it when out != nullptr (the device
-// passes go_float_put, the host the formatter of upsert.cpp).
+// passes go_float_put, the host the formatter of go_marshal.cpp).
 #pragma once
 #include <stdint.h>
 

@@ -4,22 +4,15 @@
 // exact-size and short output buffers, spans that leave the body, malformed escapes -- and, given a corpus file, every
 // document of it in both modes: the decoded spans must equal gpudiff_target_host's strings.
 //
-// The corpus file is the write path's test corpus, each document behind its length (u32, little-endian):
+// The corpus file is the write path's test corpus (tests/upsert_cases.py: the KAT documents, fixture_docs(),
+// boundary_docs() and synthetic_docs(), in that order), each document behind its length (u32, little-endian).
+// tests/test_go_marshal_sanitize.py writes it.
 //
-//   python -c "import struct, sys; from tests import upsert_cases as U; \
-//     d = [k[1] for k in U.KAT] + U.fixture_docs() + U.boundary_docs() + U.synthetic_docs(); \
-//     sys.stdout.buffer.write(b''.join(struct.pack('<I', len(x)) + x for x in d))" > /tmp/corpus.bin
+// The host marshaller is go_marshal.cpp over json.cpp and needs nothing else of the library
+// (tests/test_go_marshal_sanitize.py builds and runs this program so):
 //
-// Build upsert.cpp and json.cpp with the sanitizers and link them with the library's other objects (after
-// `python kcp_amd/build.py`):
-//
-//   S="-Xarch_host -fsanitize=address,undefined -fno-sanitize-recover=undefined"
-//   F="-O1 -g -std=c++17 -fPIC --offload-arch=gfx950 -Iinclude"
-//   hipcc $F $S -c kcp_amd/csrc/upsert.cpp -o /tmp/upsert.o
-//   hipcc $F $S -c kcp_amd/csrc/json.cpp -o /tmp/json.o
-//   hipcc $F $S -c tools/targets_sanitize.cpp -o /tmp/main.o
-//   hipcc --offload-arch=gfx950 -fsanitize=address,undefined /tmp/main.o /tmp/upsert.o /tmp/json.o \
-//       $(ls kcp_amd/_build/*.o | grep -v -e upsert.cpp.o -e json.cpp.o -e synth.cpp.o) -lpthread -o /tmp/tgs
+//   S="-fsanitize=address,undefined -fno-sanitize-recover=undefined"
+//   g++ -O1 -g -std=c++17 -Wall -Werror $S -Iinclude -o /tmp/tgs tools/targets_sanitize.cpp kcp_amd/csrc/go_marshal.cpp kcp_amd/csrc/json.cpp
 //   /tmp/tgs /tmp/corpus.bin
 //
 // Exit status 0 and "ok" = every answer matched and the sanitizers saw nothing.

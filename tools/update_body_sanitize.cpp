@@ -3,16 +3,11 @@
 // gpudiff_update_body_host and gpudiff_splice_resource_version: the known answers of tests/test_update_body.py,
 // exact-size and short output buffers, and descriptors that do not fit the body.
 //
-// Build upsert.cpp and json.cpp with the sanitizers and link them with the library's other objects (after
-// `python kcp_amd/build.py`):
+// The host marshaller is go_marshal.cpp over json.cpp and needs nothing else of the library
+// (tests/test_go_marshal_sanitize.py builds and runs this program so):
 //
-//   S="-Xarch_host -fsanitize=address,undefined -fno-sanitize-recover=undefined"
-//   F="-O1 -g -std=c++17 -fPIC --offload-arch=gfx950 -Iinclude"
-//   hipcc $F $S -c kcp_amd/csrc/upsert.cpp -o /tmp/upsert.o
-//   hipcc $F $S -c kcp_amd/csrc/json.cpp -o /tmp/json.o
-//   hipcc $F $S -c tools/update_body_sanitize.cpp -o /tmp/main.o
-//   hipcc --offload-arch=gfx950 -fsanitize=address,undefined /tmp/main.o /tmp/upsert.o /tmp/json.o \
-//       $(ls kcp_amd/_build/*.o | grep -v -e upsert.cpp.o -e json.cpp.o -e synth.cpp.o) -lpthread -o /tmp/ubs
+//   S="-fsanitize=address,undefined -fno-sanitize-recover=undefined"
+//   g++ -O1 -g -std=c++17 -Wall -Werror $S -Iinclude -o /tmp/ubs tools/update_body_sanitize.cpp kcp_amd/csrc/go_marshal.cpp kcp_amd/csrc/json.cpp
 //   /tmp/ubs
 //
 // Exit status 0 and "ok" = every answer matched and the sanitizers saw nothing.
