@@ -104,6 +104,9 @@ enum {
 #define GPUDIFF_OPT_TIMING 0x1u          /* record per-kernel HIP event times (gpudiff_last_timings) */
 #define GPUDIFF_OPT_K2_ROWS 0x40u        /* diagnostic (the A/B, the tests): K2 reads the 64-B rows although the
                                             batch's 16-B pair descriptors are current; results do not change */
+#define GPUDIFF_OPT_NO_IMAGE 0x20u       /* honoured at gpudiff_dbatch_append: the appended pairs get no compare image
+                                            (below) and their ordinary descriptors; results do not change.  The
+                                            in-build A/B reference beside GPUDIFF_OPT_K2_ROWS */
 #define GPUDIFF_OPT_ARENA_SHIFT 21u      /* 4 bits, test hook: shrink the per-wave path arena 2^k-fold (forces
                                             pairs through the deferred K4 path) */
 #define GPUDIFF_OPT_DEVICE_ENCODE 0x2000000u /* gpudiff_submit / single-pair helpers: raw JSON up, kernel K0
@@ -121,7 +124,7 @@ enum {
                                                 inside gpudiff_wait (gpudiff_result_path_values) */
 #define GPUDIFF_OPT_KNOWN                                                                                         \
     (GPUDIFF_OPT_TIMING | (0xFu << GPUDIFF_OPT_ARENA_SHIFT) | GPUDIFF_OPT_DEVICE_ENCODE | GPUDIFF_OPT_PATH_STRINGS | \
-     GPUDIFF_OPT_SMALL_PASS | GPUDIFF_OPT_PATH_VALUES | GPUDIFF_OPT_K2_ROWS)
+     GPUDIFF_OPT_SMALL_PASS | GPUDIFF_OPT_PATH_VALUES | GPUDIFF_OPT_K2_ROWS | GPUDIFF_OPT_NO_IMAGE)
 
 /* GPUDIFF_OPT_SMALL_PASS: the largest pass the fused kernel takes (64 chunks of 64 pairs: its finishing block scans
  * the chunks with one lane each), and the most changed paths it finishes itself -- a pass with more is run again as
@@ -301,7 +304,9 @@ int gpudiff_hbatch_info_get(const gpudiff_hbatch* hb, gpudiff_hbatch_info* info)
  * GPUDIFF_OBJ_SPEC_KEYS_EQ (gpudiff_format.h) states that both sides' spec keys[] are equal, and the whole 128-byte
  * lines holding only those keys are then not read or compared; with GPUDIFF_OBJ_SPEC_SHAPE_EQ beside it the row states
  * the same of both sides' spec metas[], and the lines holding only keys and metas are not read.  A caller that cannot
- * vouch for a bit leaves it 0. */
+ * vouch for a bit leaves it 0.  A row that carries both bits (and no decode error) is streamed from the batch's compare
+ * image (gpudiff_dbatch_set_image_capacity), which holds none of its spec keys or metas; with
+ * GPUDIFF_OBJ_STAT_SHAPE_EQ beside them none of its status keys or metas either. */
 int gpudiff_hbatch_create(gpudiff_ctx* ctx, uint64_t pool_bytes, size_t n_pairs, uint64_t total_leaves,
                           gpudiff_hbatch** out, uint8_t** pool, gpudiff_pair_row** rows);
 /* reuses a host batch (staging ring): waits for its last H2D copy, grows the
@@ -324,6 +329,22 @@ int gpudiff_dbatch_create_view(gpudiff_ctx* ctx, const gpudiff_dbatch* base, gpu
 /* async H2D of hb into the batch (rows rebased onto the batch's pool) */
 int gpudiff_dbatch_append(gpudiff_ctx* ctx, gpudiff_dbatch* db, const gpudiff_hbatch* hb);
 int gpudiff_dbatch_reset(gpudiff_ctx* ctx, gpudiff_dbatch* db);
+/* The compare image: a second device allocation per batch, made by its first append, into which every append also
+ * writes a compacted copy of what the decision kernel must compare of each shape-equal pair (gpudiff_format.h,
+ * gpudiff_pair_image_parts): the values and the string tails, without the keys and metas the encoder has proved
+ * equal.  The decision kernel streams such a pair from the image; everything else (joins, exports, the pool, the
+ * rows) is unchanged.  Its capacity defaults to the pool's (an image is never larger than its blobs); when it is
+ * full, or cannot be allocated, the remaining pairs are streamed from the pool as before -- an append never fails
+ * for the image.  gpudiff_dbatch_set_image_capacity sets the capacity in bytes before the batch's first append
+ * (GPUDIFF_E_STATE after it, GPUDIFF_E_INVAL on a view); 0: no image.  The ring batches behind gpudiff_submit are
+ * diffed once and have none. */
+int gpudiff_dbatch_set_image_capacity(gpudiff_dbatch* db, uint64_t bytes);
+typedef struct gpudiff_image_stats {
+    uint64_t bytes_used; /* image bytes written (both sides of every imaged pair) */
+    uint64_t capacity;   /* bytes allocated; 0: no image (none wanted, not yet appended, or the allocation failed) */
+    uint64_t pairs;      /* resident pairs streamed from the image */
+} gpudiff_image_stats;
+int gpudiff_dbatch_image_stats(const gpudiff_dbatch* db, gpudiff_image_stats* st);
 int gpudiff_dbatch_stats_get(const gpudiff_dbatch* db, gpudiff_batch_stats* st);
 int gpudiff_dbatch_device_view(const gpudiff_dbatch* db, gpudiff_device_view* v);
 /* async device-to-device copy of a diffed batch's results into caller memory
@@ -379,6 +400,9 @@ int gpudiff_rows_stream_bytes(const gpudiff_pair_row* rows, size_t n, uint64_t* 
 /* *out = the same sum with every bit honoured: what the decision kernel really reads for the rows from their
  * descriptors, key and shape holes left out (16 B + 32 B per streamed chunk, a pair) */
 int gpudiff_rows_read_bytes(const gpudiff_pair_row* rows, size_t n, uint64_t* out);
+/* *out = the sum of gpudiff_pair_image_bytes: what the decision kernel reads for the rows when every pair that can
+ * be is streamed from the compare image (gpudiff_rows_read_bytes where none is) */
+int gpudiff_rows_image_read_bytes(const gpudiff_pair_row* rows, size_t n, uint64_t* out);
 
 /* ---- diff (the hot path) ---- */
 /* enqueue K2..K6 on the context stream; returns immediately */

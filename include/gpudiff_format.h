@@ -85,6 +85,12 @@
  * pair it compares every value and tail byte on every pass, and trusts the keys and metas inside whole lines as it
  * trusts the sizes.  Additive like the bit above: the object stores, K0 and an older encoder leave it 0. */
 #define GPUDIFF_OBJ_SPEC_SHAPE_EQ 0x10u
+/* flags_b only: the same fact about the status region -- stat_l_a == stat_l_b > 0, both sides have a status key, and
+ * the two status keys[] and the two status metas[] are element for element equal (so stat_ar_a == stat_ar_b).  Stated
+ * by PairEncoder::encode_flat, which holds both sides' status leaves sorted by hash, never on a decode-error row.  It
+ * is read only where a batch's compare image is built (gpudiff_pair_image_parts): the image of such a pair keeps the
+ * status vals[] and arena alone.  Additive: every other producer of rows leaves it 0. */
+#define GPUDIFF_OBJ_STAT_SHAPE_EQ 0x20u
 /* object store: the path table kept after a resident blob's segments (the
  * "trailer"), which makes the store's old-vs-new path check exact.  Its n
  * entries are the region leaves and all their ancestors except the root,
@@ -230,6 +236,16 @@ GPUDIFF_HD static inline uint64_t gpudiff_pair_compare_bytes(const gpudiff_pair_
 #define GPUDIFF_PD_SIZE_MAX 0x7FFFFu  /* 16-B units: segments below 8 MiB */
 #define GPUDIFF_PD_ESCAPE 0xFFFFFFFFu
 #define GPUDIFF_PD_SHAPE_L 0x40000u   /* in the skip L field: the hole is the shape hole, L the low 18 bits */
+/* The image form (gpudiff_pair_desc_pack_image): the descriptor of a fictitious row whose two blobs are the pair's
+ * sides in the batch's compare image -- words 0, 1 in 128-B units from the image's base, A's field the image's spec
+ * part, the status field its status part, the seven bits the real row's.  Its mark is the skip L field all ones under
+ * SPEC_EQ with A's field below GPUDIFF_PD_IMAGE_SPEC_MAX.  gpudiff_pair_desc_pack writes all ones there in two corners
+ * only -- a key hole's L = 0x7FFFF (then A's field is 0x7FFFF too: 16 L <= the segment) and a shape hole's
+ * L | GPUDIFF_PD_SHAPE_L with L = 0x3FFFF (then A's field is 0x3FFFF) -- so the bound on A's field keeps the two
+ * forms apart; a pair whose image spec part is that large is not imaged.  gpudiff_pair_desc_unpack reports the mark as
+ * GPUDIFF_PD_IMAGE in gpudiff_pair_geom::bits (no descriptor bit: the seven above fill the field). */
+#define GPUDIFF_PD_IMAGE 0x80u
+#define GPUDIFF_PD_IMAGE_SPEC_MAX 0x3FFFFu
 
 typedef struct gpudiff_pair_desc {
     uint32_t w[4];
@@ -341,9 +357,14 @@ GPUDIFF_HD static inline gpudiff_pair_geom gpudiff_pair_desc_unpack(uint32_t w0,
     const int eq = (bits & GPUDIFF_PD_SPEC_EQ) != 0u;
     /* L <= A's field: below GPUDIFF_PD_SHAPE_L there, a skip field at or above it is L | GPUDIFF_PD_SHAPE_L */
     const int shape = eq && f1 >= GPUDIFF_PD_SHAPE_L && (w2 & GPUDIFF_PD_SIZE_MAX) < GPUDIFF_PD_SHAPE_L;
-    return gpudiff_pair_geom_of((uint64_t)w0 << 7, (uint64_t)w1 << 7, seg_a, eq ? seg_a : f1 << 4,
-                                ((w3 >> (2u * GPUDIFF_PD_SIZE_BITS - 32u)) & GPUDIFF_PD_SIZE_MAX) << 4, bits,
-                                eq ? (shape ? f1 & (GPUDIFF_PD_SHAPE_L - 1u) : f1) : 0u, shape);
+    /* the image form: offsets from the image's base, no hole (the image holds no key and no meta to step over) */
+    const int image = eq && f1 == GPUDIFF_PD_SIZE_MAX && (w2 & GPUDIFF_PD_SIZE_MAX) < GPUDIFF_PD_IMAGE_SPEC_MAX;
+    gpudiff_pair_geom g =
+        gpudiff_pair_geom_of((uint64_t)w0 << 7, (uint64_t)w1 << 7, seg_a, eq ? seg_a : f1 << 4,
+                             ((w3 >> (2u * GPUDIFF_PD_SIZE_BITS - 32u)) & GPUDIFF_PD_SIZE_MAX) << 4, bits,
+                             (eq && !image) ? (shape ? f1 & (GPUDIFF_PD_SHAPE_L - 1u) : f1) : 0u, shape && !image);
+    if (image) g.bits |= GPUDIFF_PD_IMAGE;
+    return g;
 }
 
 /* the bytes the descriptor kernel reads for one pair: its 16-B descriptor and both sides' streamed chunks, key and
@@ -354,6 +375,76 @@ GPUDIFF_HD static inline uint64_t gpudiff_pair_stream_bytes(const gpudiff_pair_r
     const gpudiff_pair_geom g = gpudiff_pair_desc_is_escape(d.w[3]) ? gpudiff_pair_row_geom(r)
                                                                    : gpudiff_pair_desc_unpack(d.w[0], d.w[1], d.w[2], d.w[3]);
     return sizeof(gpudiff_pair_desc) + 32ull * ((uint64_t)g.n1 + g.n2);
+}
+
+/* ---- the compare image (DESIGN.md §5 "Compare image"): for a row with no decode error, equal spec sizes and both
+ * GPUDIFF_OBJ_SPEC_KEYS_EQ and GPUDIFF_OBJ_SPEC_SHAPE_EQ, gpudiff_dbatch_append also writes a compacted copy of what K2
+ * must compare into a second allocation.  Per side, 128-B aligned, A then B:
+ *
+ *   spec vals[L] (zero padded to 16) | spec arena
+ *   | the status region, when its sizes are equal and B has a status key: vals[Lt] (zero padded to 16) | status arena
+ *     under GPUDIFF_OBJ_STAT_SHAPE_EQ, the whole status segment otherwise
+ *   | zeros to 128
+ *
+ * *spec, *stat: the two parts' bytes (multiples of 16); returns 0 for a row that is not imaged (its ordinary descriptor
+ * is the escape, or its image spec part would not leave the mark free).  Chunk k of a part whose keys and metas were
+ * dropped is chunk k of the segment below ceil(L / 2) and chunk k + L - ceil(L / 2) from there on (stream_paths.h). */
+GPUDIFF_HD static inline int gpudiff_pair_image_parts(const gpudiff_pair_row* r, uint32_t* spec, uint32_t* stat) {
+    const uint32_t need = GPUDIFF_OBJ_SPEC_KEYS_EQ | GPUDIFF_OBJ_SPEC_SHAPE_EQ;
+    *spec = *stat = 0u;
+    if ((r->flags_a | r->flags_b) & GPUDIFF_OBJ_DECODE_ERR) return 0;
+    if (r->spec_l_a != r->spec_l_b || r->spec_ar_a != r->spec_ar_b || (r->flags_b & need) != need) return 0;
+    {
+        const gpudiff_pair_desc d = gpudiff_pair_desc_pack(r);
+        const uint64_t s = 16ull * (((uint64_t)r->spec_l_a + 1u) >> 1) + r->spec_ar_a;
+        const int stat_sz = (r->flags_b & GPUDIFF_OBJ_HAS_STATUS) && r->stat_l_a == r->stat_l_b &&
+                            r->stat_ar_a == r->stat_ar_b;
+        if (gpudiff_pair_desc_is_escape(d.w[3]) || (s >> 4) >= GPUDIFF_PD_IMAGE_SPEC_MAX) return 0;
+        *spec = (uint32_t)s;
+        if (stat_sz)
+            *stat = (r->flags_b & GPUDIFF_OBJ_STAT_SHAPE_EQ)
+                        ? (uint32_t)(16ull * (((uint64_t)r->stat_l_a + 1u) >> 1) + r->stat_ar_a)
+                        : (uint32_t)gpudiff_seg_bytes(r->stat_l_a, r->stat_ar_a);
+    }
+    return 1;
+}
+/* the image bytes of one side of the pair (a multiple of GPUDIFF_BLOB_ALIGN; B's side follows A's); 0: not imaged */
+GPUDIFF_HD static inline uint64_t gpudiff_pair_image_side(const gpudiff_pair_row* r) {
+    uint32_t s, t;
+    if (!gpudiff_pair_image_parts(r, &s, &t)) return 0u;
+    return ((uint64_t)s + t + (GPUDIFF_BLOB_ALIGN - 1u)) & ~(uint64_t)(GPUDIFF_BLOB_ALIGN - 1u);
+}
+/* the image form of the row's descriptor, its sides at bytes img_a and img_b of the image; the escape (K2 then reads
+ * the row and the pool) when the row is not imaged or an offset does not fit */
+GPUDIFF_HD static inline gpudiff_pair_desc gpudiff_pair_desc_pack_image(const gpudiff_pair_row* r, uint64_t img_a,
+                                                                        uint64_t img_b) {
+    gpudiff_pair_desc d;
+    uint32_t s, t;
+    if (!gpudiff_pair_image_parts(r, &s, &t) || ((img_a | img_b) & (GPUDIFF_BLOB_ALIGN - 1u)) != 0u ||
+        (img_a >> 7) > 0xFFFFFFFFull || (img_b >> 7) > 0xFFFFFFFFull) {
+        d.w[0] = d.w[1] = d.w[2] = d.w[3] = GPUDIFF_PD_ESCAPE;
+        return d;
+    }
+    {
+        const uint64_t zw = (uint64_t)(s >> 4) | ((uint64_t)GPUDIFF_PD_SIZE_MAX << GPUDIFF_PD_SIZE_BITS) |
+                            ((uint64_t)(t >> 4) << (2u * GPUDIFF_PD_SIZE_BITS)) |
+                            ((uint64_t)gpudiff_pair_row_bits(r) << (3u * GPUDIFF_PD_SIZE_BITS));
+        d.w[0] = (uint32_t)(img_a >> 7);
+        d.w[1] = (uint32_t)(img_b >> 7);
+        d.w[2] = (uint32_t)zw;
+        d.w[3] = (uint32_t)(zw >> 32);
+    }
+    return d;
+}
+/* the bytes the descriptor kernel reads for one pair of a batch that images every row it can: the descriptor and both
+ * image sides' streamed chunks; gpudiff_pair_stream_bytes for a row that is not imaged */
+GPUDIFF_HD static inline uint64_t gpudiff_pair_image_bytes(const gpudiff_pair_row* r) {
+    const gpudiff_pair_desc d = gpudiff_pair_desc_pack_image(r, 0u, 0u);
+    if (gpudiff_pair_desc_is_escape(d.w[3])) return gpudiff_pair_stream_bytes(r);
+    {
+        const gpudiff_pair_geom g = gpudiff_pair_desc_unpack(d.w[0], d.w[1], d.w[2], d.w[3]);
+        return sizeof(gpudiff_pair_desc) + 32ull * ((uint64_t)g.n1 + g.n2);
+    }
 }
 
 GPUDIFF_HD static inline uint32_t gpudiff_meta(uint32_t tag, uint32_t len) { return (len << 3) | tag; }

@@ -1088,10 +1088,26 @@ const OptSmallPass = uint32(C.GPUDIFF_OPT_SMALL_PASS)
 // encoder states both.  ObjSpecKeysEq: both sides' spec keys[] are element for element equal.  ObjSpecShapeEq, only
 // beside it: the spec metas[] (every leaf's type tag and byte length) are equal too.  K2 leaves the whole 128-byte
 // lines that hold only those arrays out of its stream, so a caller that cannot vouch for a bit leaves it 0.
+// ObjStatShapeEq: both sides have a status key and status leaves, and the status keys[] and metas[] are equal; a
+// device batch's compare image then holds neither for the pair.
 const (
 	ObjSpecKeysEq  = uint32(C.GPUDIFF_OBJ_SPEC_KEYS_EQ)
 	ObjSpecShapeEq = uint32(C.GPUDIFF_OBJ_SPEC_SHAPE_EQ)
+	ObjStatShapeEq = uint32(C.GPUDIFF_OBJ_STAT_SHAPE_EQ)
 )
+
+// OptNoImage: device batches appended under it get no compare image (gpudiff.h); results do not change.
+const OptNoImage = uint32(C.GPUDIFF_OPT_NO_IMAGE)
+
+// RowsImageReadBytes sums what the decision kernel reads for n pair rows when every pair that can be is streamed from
+// the batch's compare image (gpudiff_rows_image_read_bytes); RowsReadBytes where none is.
+func RowsImageReadBytes(rows unsafe.Pointer, n int) (uint64, error) {
+	var out C.uint64_t
+	if err := errOf(C.gpudiff_rows_image_read_bytes((*C.gpudiff_pair_row)(rows), C.size_t(n), &out)); err != nil {
+		return 0, err
+	}
+	return uint64(out), nil
+}
 
 // RowsReadBytes sums what the decision kernel reads for n pair rows (gpudiff_pair_row, 64 bytes each) from their
 // descriptors, key and shape holes left out (gpudiff_rows_read_bytes).  For measurements; the shard weight stays the

@@ -82,6 +82,7 @@ static DiffBuffers buffers_of(gpudiff_ctx* c, gpudiff_dbatch* d) {
     b.rows = d->rows;
     b.desc = (d->desc_gen == d->rows_gen && !(c->flags & GPUDIFF_OPT_K2_ROWS)) ? d->desc : nullptr;
     b.pool = d->pool;
+    b.image = b.desc ? d->image : nullptr;
     b.pair_ids = d->pair_ids;
     b.n_pairs = (uint32_t)d->n_pairs;
     b.flags = d->flags;
@@ -436,6 +437,8 @@ static void view_sync(gpudiff_dbatch* d) {
     d->rows_gen = b->rows_gen;
     d->desc = b->desc;
     d->desc_gen = b->desc_gen;
+    d->image = b->image;  // borrowed like desc, whose image-form descriptors count from it
+    d->image_cap = b->image_cap;
 }
 
 // every per-pass output of a batch (a view has only these)
@@ -446,7 +449,7 @@ static int alloc_outputs(gpudiff_dbatch* d) {
     const uint64_t ntiles = 4 * (np / 4096 + 2);  // scan tile sums (4 x u32 for the chunk scan)
     uint4* cc = nullptr;
     if ((rc = dalloc(&d->flags, np)) || (rc = dalloc(&d->caps, np)) || (rc = dalloc(&cc, nchunks)) ||
-        (rc = dalloc(&d->summary, kSummaryWords)) || (rc = dalloc(&d->spec_ids, np)) || (rc = dalloc(&d->status_ids, np)) ||
+        (rc = dalloc(&d->summary, kSummaryAlloc)) || (rc = dalloc(&d->spec_ids, np)) || (rc = dalloc(&d->status_ids, np)) ||
         (rc = dalloc(&d->dirty_ids, np)) || (rc = dalloc(&d->dirty_idx, np)) || (rc = dalloc(&d->scratch_off, np)) ||
         (rc = dalloc(&d->path_count, np)) || (rc = dalloc(&d->path_off, np + 1)) ||
         (rc = dalloc(&d->path_src, np)) || (rc = dalloc(&d->path_cnt, np)) || (rc = dalloc(&d->nbits, np)) ||
@@ -458,6 +461,56 @@ static int alloc_outputs(gpudiff_dbatch* d) {
     }
     d->chunk_counts = cc;
     if (hipEventCreateWithFlags(&d->done, hipEventDisableTiming) != hipSuccess) return GPUDIFF_E_DEVICE;
+    return GPUDIFF_OK;
+}
+
+// The batch's compare image and the builder's scratch for a chunk of n rows, allocated on demand.  false: these rows
+// get no image -- switched off (the context's GPUDIFF_OPT_NO_IMAGE, capacity 0) or not to be had (an allocation
+// failed: the image stays off for the batch's life, a failed scratch only for this append).
+static bool image_ready(gpudiff_ctx* c, gpudiff_dbatch* d, uint64_t n) {
+    if ((c->flags & GPUDIFF_OPT_NO_IMAGE) || d->image_off || d->pool_borrowed) return false;
+    if (!d->image) {
+        const uint64_t cap = (d->image_cap_req == ~0ull ? d->pool_cap : d->image_cap_req) & ~127ull;
+        if (!cap || hipMalloc((void**)&d->image, cap) != hipSuccess) {
+            (void)hipGetLastError();  // not an error of the append
+            d->image = nullptr;
+            d->image_off = true;
+            return false;
+        }
+        d->image_cap = cap;
+    }
+    if (n > d->image_scan_n) {
+        if (d->image_scan) {
+            if (hipStreamSynchronize(c->stream) != hipSuccess) return false;
+            (void)hipFree(d->image_scan);
+            d->image_scan = nullptr;
+            d->image_scan_n = 0;
+        }
+        const uint64_t want = std::max<uint64_t>(n, 1u << 16);
+        if (hipMalloc((void**)&d->image_scan, image_scan_words((uint32_t)want) * sizeof(uint64_t)) != hipSuccess) {
+            (void)hipGetLastError();
+            d->image_scan = nullptr;
+            return false;
+        }
+        d->image_scan_n = want;
+    }
+    return true;
+}
+
+int gpudiff_dbatch_set_image_capacity(gpudiff_dbatch* d, uint64_t bytes) {
+    if (!d || d->base) return GPUDIFF_E_INVAL;
+    if (d->n_pairs || d->image) return GPUDIFF_E_STATE;
+    d->image_cap_req = bytes;
+    d->image_off = bytes < 128u;
+    return GPUDIFF_OK;
+}
+
+int gpudiff_dbatch_image_stats(const gpudiff_dbatch* d, gpudiff_image_stats* st) {
+    if (!d || !st) return GPUDIFF_E_INVAL;
+    if (d->base) d = d->base;
+    st->bytes_used = d->image_used;
+    st->capacity = d->image ? d->image_cap : 0u;
+    st->pairs = d->image_pairs;
     return GPUDIFF_OK;
 }
 
@@ -475,10 +528,21 @@ int gpudiff_dbatch_append(gpudiff_ctx* c, gpudiff_dbatch* d, const gpudiff_hbatc
                           c->stream));
     if (hb->used) HIPCHK(hipEventRecord(hb->used, c->stream));
     HIPCHK(launch_rebase(c->stream, d->rows, begin, end, base, d->pair_ids, d->desc));
+    const bool imaging = image_ready(c, d, hb->n);
+    if (imaging)
+        HIPCHK(launch_image_build(c->stream, d->rows, begin, end, d->image_scan, d->image_cursor, d->image_cap, d->pool,
+                                  d->image, d->desc));
     uint64_t cb = 0, vb = 0;
     for (size_t i = 0; i < hb->n; i++) {
         const gpudiff_pair_row& r = hb->rows[i];
         cb += pair_compare_bytes(r);
+        if (imaging) {  // the builder's placement, restated: an exclusive sum, a pair imaged while it ends inside
+            gpudiff_pair_row rr = r;
+            rr.off_a += base, rr.off_b += base;
+            const uint64_t ib = 2u * gpudiff_pair_image_side(&rr);
+            if (ib && d->image_cursor + ib <= d->image_cap) d->image_used = d->image_cursor + ib, d->image_pairs++;
+            d->image_cursor += ib;
+        }
         if ((r.flags_a | r.flags_b) & GPUDIFF_OBJ_DECODE_ERR) continue;
         vb += blob_value_bytes(hb->pool + r.off_a, r.spec_l_a, r.spec_ar_a, r.stat_l_a) +
               blob_value_bytes(hb->pool + r.off_b, r.spec_l_b, r.spec_ar_b, r.stat_l_b);
@@ -501,6 +565,7 @@ int gpudiff_dbatch_reset(gpudiff_ctx* c, gpudiff_dbatch* d) {
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(c->stream));
     d->pool_used = d->n_pairs = d->leaves = d->compare_bytes = d->value_bytes = d->size_hint_bytes = 0;
+    d->image_cursor = d->image_used = d->image_pairs = 0;
     d->ticket = 0;
     d->rows_gen++;
     return GPUDIFF_OK;
@@ -570,7 +635,7 @@ int gpudiff_dbatch_result_slot(gpudiff_ctx* c, gpudiff_dbatch* d, uint32_t slot)
     if (!d->summary_alt) {  // all three buffers or none (a half-allocated slot would swap in a null list)
         const uint64_t np = std::max<uint64_t>(d->max_pairs, 1);
         uint32_t *a = nullptr, *b = nullptr, *sm = nullptr;
-        if ((rc = dalloc(&a, np)) || (rc = dalloc(&b, np)) || (rc = dalloc(&sm, kSummaryWords))) {
+        if ((rc = dalloc(&a, np)) || (rc = dalloc(&b, np)) || (rc = dalloc(&sm, kSummaryAlloc))) {
             for (uint32_t* p : {a, b, sm})
                 if (p) (void)hipFree(p);
             return rc;
@@ -618,6 +683,14 @@ int gpudiff_rows_stream_bytes(const gpudiff_pair_row* rows, size_t n, uint64_t* 
         r.flags_b &= ~GPUDIFF_OBJ_SPEC_SHAPE_EQ;
         sum += gpudiff_pair_stream_bytes(&r);
     }
+    *out = sum;
+    return GPUDIFF_OK;
+}
+
+int gpudiff_rows_image_read_bytes(const gpudiff_pair_row* rows, size_t n, uint64_t* out) {
+    if ((n && !rows) || !out) return GPUDIFF_E_INVAL;
+    uint64_t sum = 0;
+    for (size_t i = 0; i < n; i++) sum += gpudiff_pair_image_bytes(&rows[i]);
     *out = sum;
     return GPUDIFF_OK;
 }
@@ -1107,6 +1180,8 @@ int gpudiff_submit(gpudiff_ctx* c, const gpudiff_json_pair* pairs, size_t n, gpu
             gpudiff_hbatch_free(c, hb);
             return rc;
         }
+        // a ring batch is diffed once: building an image would read and write more than that one pass saves
+        (void)gpudiff_dbatch_set_image_capacity(d, 0);
     }
     d->pool_used = d->n_pairs = d->leaves = d->compare_bytes = d->value_bytes = d->size_hint_bytes = 0;
     if ((rc = gpudiff_dbatch_append(c, d, hb)) || (rc = gpudiff_diff(c, d, ticket))) {

@@ -299,6 +299,13 @@ void PairEncoder::encode_flat(FlatObject* fa, FlatObject* fb, uint32_t pair_id, 
     bool shape_eq = keys_eq;
     for (size_t i = 0; shape_eq && i < fa->spec.size(); i++) shape_eq = fa->spec[i].meta == fb->spec[i].meta;
     if (shape_eq) row.flags_b |= GPUDIFF_OBJ_SPEC_SHAPE_EQ;
+    // the same of the status region, where both sides have a status key and leaves under it: equal counts, keys[]
+    // and metas[] (equal arenas follow); a batch's compare image then leaves the status keys and metas out too
+    const bool both_status = (fa->flags & fb->flags & GPUDIFF_OBJ_HAS_STATUS) != 0u;
+    bool stat_eq = both_status && !fa->stat.empty() && fa->stat.size() == fb->stat.size();
+    for (size_t i = 0; stat_eq && i < fa->stat.size(); i++)
+        stat_eq = (uint32_t)fa->stat[i].h == (uint32_t)fb->stat[i].h && fa->stat[i].meta == fb->stat[i].meta;
+    if (stat_eq) row.flags_b |= GPUDIFF_OBJ_STAT_SHAPE_EQ;
 }
 
 void PairEncoder::encode_nodes(const Node* a, const Node* b, uint32_t pair_id, uint32_t cluster_id,

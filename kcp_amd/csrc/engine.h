@@ -138,6 +138,17 @@ struct gpudiff_dbatch {
     // current, and K2 gets the array only then -- any other producer of rows bumps rows_gen alone and K2 reads rows
     uint4* desc = nullptr;
     uint64_t desc_gen = ~0ull;
+    // The compare image (gpudiff_format.h: gpudiff_pair_image_parts): one allocation made by the first
+    // append, image_cap bytes (gpudiff_dbatch_set_image_capacity, default the pool's capacity), filled by the appends'
+    // builder kernel and reached only through image-form descriptors -- so desc_gen covers its staleness too.  A view
+    // borrows it.  image_cursor: the image bytes of every imaged-if-it-fits pair appended so far (the next append's
+    // base; past image_cap once the image is full), image_used / image_pairs: what is in it.  image_off: no image
+    // (capacity 0, or its allocation failed).  image_scan: the builder's scratch for a chunk of image_scan_n rows.
+    uint8_t* image = nullptr;
+    uint64_t image_cap = 0, image_cap_req = ~0ull, image_cursor = 0, image_used = 0, image_pairs = 0;
+    bool image_off = false;
+    uint64_t* image_scan = nullptr;
+    uint64_t image_scan_n = 0;
     // GPUDIFF_OPT_SMALL_PASS: the result image K20 packs (small_pass.h; allocated by the batch's first small pass),
     // and whether the pass `done` stands for was a small one (collect_results reads the image then)
     uint8_t* small_image = nullptr;
@@ -300,7 +311,10 @@ inline int dalloc(T** p, uint64_t count) {
 
 inline void dfree_all(gpudiff_dbatch* d) {
     if (d->pool && !d->pool_borrowed) (void)hipFree(d->pool);
-    if (d->base) d->rows = nullptr, d->pair_ids = nullptr, d->desc = nullptr;  // a view's inputs are its base's
+    if (d->base) d->rows = nullptr, d->pair_ids = nullptr, d->desc = nullptr, d->image = nullptr;  // a view's inputs are its base's
+    if (d->image) (void)hipFree(d->image);
+    if (d->image_scan) (void)hipFree(d->image_scan);
+    d->image = nullptr, d->image_scan = nullptr;
     void* ps[] = {d->rows, d->pair_ids, d->desc, d->flags, d->caps, d->chunk_counts, d->summary, d->spec_ids,
                   d->status_ids, d->dirty_ids, d->dirty_idx, d->scratch_off, d->path_count, d->path_off,
                   d->tile_sums, d->path_src, d->path_cnt, d->arena_h, d->arena_k,

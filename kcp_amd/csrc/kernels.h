@@ -19,6 +19,7 @@ struct DiffBuffers {
     const gpudiff_pair_row* rows;
     const uint4* desc;  // the rows' 16-B descriptors (gpudiff_format.h), or nullptr: stale, or switched off
     const uint8_t* pool;
+    const uint8_t* image = nullptr;  // the batch's compare image: what desc's image-form descriptors count from
     const uint32_t* pair_ids;
     uint32_t n_pairs;
     uint8_t* flags;
@@ -73,6 +74,13 @@ struct TailPermKey {
 
 // summary[8]: K2's main item counter; summary[8 + kK2TailCounters]: its tail item counter (zeroed with the pass)
 constexpr uint32_t kK2TailCounters = 8, kSummaryWords = 8 + 2 * kK2TailCounters;
+// ... and behind the zeroed words, as one u64, image - pool of the pass's batch (0: no image), written with the zeroing:
+// K2's lanes load it where an image-form descriptor is unpacked.  (As a kernel argument it stayed in two scalar
+// registers for the whole launch, and the default kernel, which already keeps scalars in vector lanes, came out at
+// 129 VGPRs: 3 waves a SIMD instead of 4.)
+// It has a 128-byte line of its own: the words before it take every wave's ticket atomics.
+constexpr uint32_t kSummaryImageDelta = 32, kSummaryAlloc = kSummaryImageDelta + 2;
+static_assert(kSummaryImageDelta % 32 == 0 && kSummaryImageDelta >= kSummaryWords, "the delta: an aligned u64, its own line");
 // default tail: half a chunk per resident wave, in items of half a main item (in-process A/B on MI355X,
 // profiles/r02zj-r02zm: 8-pair tail items cost more than the imbalance they remove; with no tail at all
 // the main items' tickets are fetched late in the last two rounds instead)
@@ -84,6 +92,12 @@ uint32_t k2_grid_waves(const DiffBuffers& b, uint32_t nchunks);
 // rows [begin, end): offsets += base, pair_ids[i] = the row's; desc != nullptr: their K2 descriptors too
 hipError_t launch_rebase(hipStream_t s, gpudiff_pair_row* rows, uint32_t begin, uint32_t end, uint64_t base,
                          uint32_t* pair_ids, uint4* desc);
+// The compare image of the appended rows [begin, end), after launch_rebase: each imaged pair's sides into `image` from
+// byte `used` on (an exclusive sum of the chunk's image bytes) and its descriptor replaced by the image form; a pair
+// that would end past cap keeps its descriptor.  scan: image_scan_words(end - begin) u64 of device scratch.
+inline uint64_t image_scan_words(uint32_t n) { return 2ull * n + 2u + (n + 1023u) / 1024u; }
+hipError_t launch_image_build(hipStream_t s, const gpudiff_pair_row* rows, uint32_t begin, uint32_t end, uint64_t* scan,
+                              uint64_t used, uint64_t cap, const uint8_t* pool, uint8_t* image, uint4* desc);
 // object-store compaction: blob copies between the two spaces
 struct BlobMove {
     uint64_t src, dst, bytes;

@@ -24,6 +24,7 @@
 #include "../../include/gpudiff.h"
 #include "join_dev.h"
 #include "kernels.h"
+#include "scan64.h"
 #include "stream_paths.h"
 #include "wave_dev.h"
 #include "xxh64.h"
@@ -151,20 +152,30 @@ struct StreamLog {
     uint32_t cnt[2][64];             // [status][pair]
     uint32_t ent[2][64][kSpLogCap];  // sp_entry(the chunk's index in the item's stream, its differing dwords)
     uint32_t first[64], n1[64];      // a pair's first chunk in the item's stream, its streamed spec chunks
-    uint32_t hole[64];               // its key or shape hole (sp_hole_word): a logged spec chunk's place in the segment
+    uint32_t hole[64];               // its key or shape hole (sp_hole_word): a logged spec chunk's place in the segment;
+                                     // kSpHoleImage: the pair streamed from the compare image (sp_entry_unimage)
 };
 
 // The changed paths of a size-matched region from its c <= kSpLogCap logged chunks, by stream_paths.h's rule (a
 // lane per differing dword, then a lane per changed leaf): written where join_region<true> would write them, in
 // its order (ascending leaf = ascending key), with its *weq_all.  Returns the path count, or kSpRefuse with
 // nothing written that the join does not overwrite: the caller then joins the region.
+// IMG (the descriptor kernel): hole may be kSpHoleImage -- the region streamed from the compare image without its keys
+// and metas, so a logged chunk goes back to the segment through sp_entry_unimage; A, B stay the pool's views (every
+// gather below and the join read the pool, never the image).
+template <bool IMG>
 __device__ uint32_t stream_region(const RegionView& A, const RegionView& B, uint64_t seg, const uint32_t* ent,
                                   uint32_t c, uint32_t g0, uint32_t hole, uint8_t region_bit,
                                   uint64_t* __restrict__ out_h, uint8_t* __restrict__ out_k, uint32_t out_base,
                                   uint32_t lane, bool* weq_all) {
     const uint32_t nc = 4u * c;  // <= 16 candidate lanes: dword (lane & 3) of entry (lane >> 2)
     // g0: the region's first chunk; hole: the streamed index back to the chunk's place in the segment
-    const uint32_t e = lane < nc ? sp_entry_unhole(ent[lane >> 2] - sp_entry(g0, 0u), hole) : 0u;
+    uint32_t e = 0u;
+    if (lane < nc) {
+        const uint32_t e0 = ent[lane >> 2] - sp_entry(g0, 0u);
+        if (IMG && hole == kSpHoleImage) e = sp_entry_unimage(e0, A.L);
+        else e = sp_entry_unhole(e0, hole);
+    }
     const bool cand = lane < nc && ((sp_entry_dwords(e) >> (lane & 3u)) & 1u);
     const uint64_t b = sp_entry_byte(e, lane & 3u);
     const SpWhere w = sp_classify(b, A.L);
@@ -227,7 +238,11 @@ __device__ uint32_t stream_region(const RegionView& A, const RegionView& B, uint
 }
 
 // join_pair<true> for K2's own pairs: a size-matched region the stream found dirty is emitted from the wave's
-// log when the rule allows (*n_stream counts those), joined otherwise; spec, status, sentinel as in join_pair
+// log when the rule allows (*n_stream counts those), joined otherwise; spec, status, sentinel as in join_pair.
+// IMG: a pair streamed from the compare image (its log slot's hole is kSpHoleImage) maps its spec chunks back with
+// spec_l, and its status chunks with stat_l when the row carries GPUDIFF_OBJ_STAT_SHAPE_EQ (the image then holds the
+// status vals and arena alone; otherwise the status segment was copied whole and its chunks are the segment's)
+template <bool IMG>
 __device__ uint32_t stream_pair(const gpudiff_pair_row& r, uint32_t f, const uint8_t* pool, uint64_t mask,
                                 uint64_t* out_h, uint8_t* out_k, uint32_t base, uint32_t lane, uint32_t* noop,
                                 const StreamLog* log, uint32_t k, bool log_ok, uint32_t* n_stream) {
@@ -240,8 +255,8 @@ __device__ uint32_t stream_pair(const gpudiff_pair_row& r, uint32_t f, const uin
         const uint32_t g0 = uni(log->first[k]);
         uint32_t got = kSpRefuse;
         if (c >= 1u && c <= kSpLogCap)
-            got = stream_region(A, B, seg_bytes(r.spec_l_a, r.spec_ar_a), log->ent[0][k], c, g0, uni(log->hole[k]), 0,
-                                out_h, out_k, base + n, lane, &spec_weq);
+            got = stream_region<IMG>(A, B, seg_bytes(r.spec_l_a, r.spec_ar_a), log->ent[0][k], c, g0, uni(log->hole[k]),
+                                     0, out_h, out_k, base + n, lane, &spec_weq);
         if (got == kSpRefuse) got = join_region<true>(A, B, 0, out_h, out_k, base + n, lane, &spec_weq);
         else (*n_stream)++;
         n += got;
@@ -252,9 +267,12 @@ __device__ uint32_t stream_pair(const gpudiff_pair_row& r, uint32_t f, const uin
         const uint32_t c = log_ok ? uni(log->cnt[1][k]) : 0u;
         const uint32_t g0 = uni(log->first[k]) + uni(log->n1[k]);
         uint32_t got = kSpRefuse;
+        uint32_t th = 0u;
+        if constexpr (IMG)
+            th = (uni(log->hole[k]) == kSpHoleImage && (r.flags_b & GPUDIFF_OBJ_STAT_SHAPE_EQ)) ? kSpHoleImage : 0u;
         if (c >= 1u && c <= kSpLogCap)
-            got = stream_region(A, B, seg_bytes(r.stat_l_a, r.stat_ar_a), log->ent[1][k], c, g0, 0u,
-                                GPUDIFF_PATH_REGION_STATUS, out_h, out_k, base + n, lane, &stat_weq);
+            got = stream_region<IMG>(A, B, seg_bytes(r.stat_l_a, r.stat_ar_a), log->ent[1][k], c, g0, th,
+                                     GPUDIFF_PATH_REGION_STATUS, out_h, out_k, base + n, lane, &stat_weq);
         if (got == kSpRefuse)
             got = join_region<true>(A, B, GPUDIFF_PATH_REGION_STATUS, out_h, out_k, base + n, lane, &stat_weq);
         else (*n_stream)++;
@@ -710,7 +728,10 @@ __device__ __forceinline__ uint32_t lds_add(uint32_t* p, uint32_t v) {
 // DESC (the default kernel and its timeline build): an item's lanes read their pairs' 16-B descriptors (desc,
 // gpudiff_format.h) instead of the 64-B rows.  A lane loads its row only when its descriptor is the escape (before
 // the stream) or when its pair turns out dirty in any way but the status-absent sentinel under seed 0 (after it: the
-// leaf counts behind the K4 cap and the seed's value are not in the descriptor).
+// leaf counts behind the K4 cap and the seed's value are not in the descriptor).  A descriptor in the image form
+// (GPUDIFF_PD_IMAGE) counts its offsets from the batch's compare image: image - pool (summary[kSummaryImageDelta], a
+// u64 written with the pass's zeroing) goes into the lane's two offsets where the descriptor is unpacked, so the stream
+// itself does not know; the pair's log slot says so (kSpHoleImage) for the lanes that emit its paths.
 template <int U, int MINB, bool PROF = false, bool HELP = false, bool DESC = false>
 __global__ __launch_bounds__(256, MINB) void k_compare_flat(const gpudiff_pair_row* __restrict__ rows,
                                                       const uint8_t* __restrict__ pool, uint32_t n,
@@ -925,7 +946,8 @@ __global__ __launch_bounds__(256, MINB) void k_compare_flat(const gpudiff_pair_r
         [[maybe_unused]] uint32_t hole = 0;  // DESC: the pair's key or shape hole (sp_hole_word)
         // DESC: the pair's GPUDIFF_PD_* bits | kPdRow (its descriptor is the escape): all the stream leaves alive
         [[maybe_unused]] uint32_t dbits = 0;
-        constexpr uint32_t kPdRow = 0x80u;
+        constexpr uint32_t kPdRow = 0x100u;
+        static_assert(kPdRow > GPUDIFF_PD_IMAGE, "the unpack's bits and this one share dbits");
         if constexpr (DESC) {
             // the geometry from the descriptor (gpudiff_pair_desc_unpack: the row's rule below, from 16-B units); an
             // escape's lane takes it from its row
@@ -950,6 +972,19 @@ __global__ __launch_bounds__(256, MINB) void k_compare_flat(const gpudiff_pair_r
             off_b += (uint64_t)g.adj_b - (uint64_t)g.adj_a;  // (each zero-extended, as the stream adds adj_a)
             adj_a = adj_b = g.adj_a;
             hole = sp_hole_word(g.hs, g.hl);
+            // an image pair: both offsets count from the image, and its hole word is kSpHoleImage -- a hole that starts
+            // past any image pair's last spec chunk (sp_hole_start(kSpHoleImage) = 2^19 - 8, its spec part padded to the
+            // line below GPUDIFF_PD_IMAGE_SPEC_MAX + 8), so the stream steps over nothing, and the word reaches the
+            // pair's log slot as it is
+            if (dbits & GPUDIFF_PD_IMAGE) {
+                // (loaded here, kept nowhere.  Wavefront scope: an ordinary cached load, one request for the wave's lanes
+                // -- at agent scope every lane's load went to L2 on its own, 10M requests to one line a pass, and the
+                // step took 12.7 ms for 7.1)
+                const uint64_t dl = __hip_atomic_load((const uint64_t*)(summary + kSummaryImageDelta), __ATOMIC_RELAXED,
+                                                      __HIP_MEMORY_SCOPE_WAVEFRONT);
+                off_a += dl, off_b += dl;
+                hole = kSpHoleImage;
+            }
         } else {
             off_a = ((uint64_t)v0.y << 32) | v0.x, off_b = ((uint64_t)v0.w << 32) | v0.z;
             err = valid && ((v3.x | v3.y) & GPUDIFF_OBJ_DECODE_ERR) != 0u;
@@ -1091,7 +1126,7 @@ __global__ __launch_bounds__(256, MINB) void k_compare_flat(const gpudiff_pair_r
                     // profiles/r06m, r06n; staging K3's whole deferrals cost K3 4.5 us a pass in LDS occupancy)
                     const gpudiff_pair_row r = rows[p0 + k];
                     if constexpr (HELP) pc = join_pair<true>(r, fk, pool, mask, ah, ak, src, lane, &nb);
-                    else pc = stream_pair(r, fk, pool, mask, ah, ak, src, lane, &nb, slog, k, total < (1u << 28), &n_stream);  // (a log entry holds 28 bits of chunk index)
+                    else pc = stream_pair<DESC>(r, fk, pool, mask, ah, ak, src, lane, &nb, slog, k, total < (1u << 28), &n_stream);  // (a log entry holds 28 bits of chunk index)
                 } else if (fk & F_SENT) {  // status-absent only (every ConfigMap/Secret update)
                     const uint32_t fa = (uint32_t)__builtin_amdgcn_readlane((int)v3.x, (int)k);
                     nb = sentinel_noop_bits(fa);
@@ -1327,6 +1362,60 @@ __global__ __launch_bounds__(256) void k_rebase_rows(gpudiff_pair_row* __restric
     }
 }
 
+// The compare image of an appended chunk (gpudiff_format.h: gpudiff_pair_image_parts; DESIGN.md §5 "Compare image").
+// First each row's image bytes, both sides (0: not imaged), for the exclusive sum that places the pairs ...
+__global__ __launch_bounds__(256) void k_image_sizes(const gpudiff_pair_row* __restrict__ rows, uint32_t begin,
+                                                     uint32_t end, uint64_t* __restrict__ sizes) {
+    const uint32_t i = begin + blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= end) return;
+    const gpudiff_pair_row r = rows[i];
+    sizes[i - begin] = 2ull * gpudiff_pair_image_side(&r);
+}
+// ... then a wave per pair copies the 16-B chunks the image keeps, A's side then B's, each zero padded to the line, and
+// replaces the pair's descriptor by the image form.  offsets[i - begin]: the pair's place after `used` (the image
+// bytes of the appends before).  A pair that would end past cap keeps the descriptor k_rebase_rows wrote; so does
+// every later one, since the offsets only grow.
+__global__ __launch_bounds__(256) void k_image_build(const gpudiff_pair_row* __restrict__ rows, uint32_t begin,
+                                                     uint32_t end, const uint64_t* __restrict__ offsets, uint64_t used,
+                                                     uint64_t cap, const uint8_t* __restrict__ pool,
+                                                     uint8_t* __restrict__ image, uint4* __restrict__ desc) {
+    const uint32_t lane = lane_id();
+    const uint32_t nw = (gridDim.x * blockDim.x) >> 6;
+    for (uint32_t p = begin + uni((blockIdx.x * blockDim.x + threadIdx.x) >> 6); p < end; p += nw) {
+        const gpudiff_pair_row r = rows[p];
+        uint32_t s = 0, t = 0;
+        if (!gpudiff_pair_image_parts(&r, &s, &t)) continue;
+        const uint64_t side = ((uint64_t)s + t + 127u) & ~127ull;
+        const uint64_t o = used + offsets[p - begin];
+        if (o + 2u * side > cap) continue;
+        const uint32_t nv = sp_image_vals(r.spec_l_a), drop = r.spec_l_a - nv;
+        const bool tsh = t != 0u && (r.flags_b & GPUDIFF_OBJ_STAT_SHAPE_EQ) != 0u;
+        const uint32_t nvt = sp_image_vals(r.stat_l_a), tdrop = tsh ? r.stat_l_a - nvt : 0u;
+        const uint32_t cs = s >> 4, ct = t >> 4, cside = (uint32_t)(side >> 4);
+        const uint32_t seg_c = (uint32_t)(seg_bytes(r.spec_l_a, r.spec_ar_a) >> 4);  // the status segment's first chunk
+        for (uint32_t x = 0; x < 2u; x++) {
+            const u32x4* src = (const u32x4*)(pool + (x ? r.off_b : r.off_a));
+            u32x4* dst = (u32x4*)(image + o + x * side);
+            for (uint32_t q = lane; q < cside; q += 64u) {
+                u32x4 v = {0u, 0u, 0u, 0u};
+                if (q < cs) {
+                    v = src[q < nv ? q : q + drop];
+                    if ((r.spec_l_a & 1u) && q == nv - 1u) v.z = v.w = 0u;  // keys[0], keys[1] beside the last value
+                } else if (q - cs < ct) {
+                    const uint32_t k = q - cs;
+                    v = src[seg_c + ((tsh && k >= nvt) ? k + tdrop : k)];
+                    if (tsh && (r.stat_l_a & 1u) && k == nvt - 1u) v.z = v.w = 0u;
+                }
+                dst[q] = v;
+            }
+        }
+        if (lane == 0) {
+            const gpudiff_pair_desc d = gpudiff_pair_desc_pack_image(&r, o, o + side);
+            if (!gpudiff_pair_desc_is_escape(d.w[3])) desc[p] = make_uint4(d.w[0], d.w[1], d.w[2], d.w[3]);
+        }
+    }
+}
+
 // ---------------------------------------------------------------- launchers
 static inline uint32_t grid_for(uint64_t waves_wanted, uint32_t cap_blocks) {
     uint64_t blocks = (waves_wanted + 3) / 4;
@@ -1345,6 +1434,24 @@ hipError_t launch_rebase(hipStream_t s, gpudiff_pair_row* rows, uint32_t begin, 
 }
 
 
+
+hipError_t launch_image_build(hipStream_t s, const gpudiff_pair_row* rows, uint32_t begin, uint32_t end, uint64_t* scan,
+                              uint64_t used, uint64_t cap, const uint8_t* pool, uint8_t* image, uint4* desc) {
+    if (end <= begin) return hipSuccess;
+    const uint32_t n = end - begin;
+    // scan: sizes[n] | offsets[n + 1] | tile sums | total (image_scan_words(n) u64)
+    uint64_t* const sizes = scan;
+    uint64_t* const offsets = scan + n;
+    uint64_t* const tiles = offsets + n + 1u;
+    uint64_t* const total = tiles + scan64_tiles(n);
+    k_image_sizes<<<(n + 255u) / 256u, 256, 0, s>>>(rows, begin, end, sizes);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    if ((e = launch_scan64_sums(s, sizes, n, tiles, total)) != hipSuccess) return e;
+    if ((e = launch_scan64_offsets(s, sizes, n, tiles, offsets)) != hipSuccess) return e;
+    k_image_build<<<grid_for(n, kPersistBlocks), 256, 0, s>>>(rows, begin, end, offsets, used, cap, pool, image, desc);
+    return hipGetLastError();
+}
 
 hipError_t launch_move_blobs(hipStream_t s, const uint8_t* src, uint8_t* dst, const BlobMove* moves, uint32_t n) {
     if (!n) return hipSuccess;
@@ -1439,9 +1546,10 @@ uint32_t k2_grid_waves(const DiffBuffers& b, uint32_t nchunks) {
 // A pass's zeroing in one launch (hipMemsetAsync is a fill kernel each): the summary words (when the pass
 // starts with this K2 launch) and the chunk counts that split chunks accumulate with atomics
 __global__ __launch_bounds__(256) void k_pass_reset(uint32_t* __restrict__ summary, uint32_t nwords,
-                                                    uint4* __restrict__ cc, uint32_t ncc) {
+                                                    uint4* __restrict__ cc, uint32_t ncc, uint64_t image_delta) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (summary && i < nwords) summary[i] = 0u;
+    if (summary && i == nwords) *(uint64_t*)(summary + kSummaryImageDelta) = image_delta;  // (thread kSummaryWords: one)
     for (uint32_t j = i; j < ncc; j += gridDim.x * 256u) cc[j] = make_uint4(0u, 0u, 0u, 0u);
 }
 
@@ -1551,8 +1659,8 @@ hipError_t launch_compare(hipStream_t s, const DiffBuffers& b) {
     {  // one launch zeroes the summary and the chunk counts split items accumulate with atomics
         const uint32_t z0 = sub ? 0u : lpt ? (((nch << sub) - lpt) >> sub) : nch - tail;
         const uint32_t ncc = nch - z0;
-        k_pass_reset<<<std::max(1u, std::min(1024u, (ncc + 255u) / 256u)), 256, 0, s>>>(b.summary, kSummaryWords,
-                                                                                        cc + z0, ncc);
+        k_pass_reset<<<std::max(1u, std::min(1024u, (ncc + 255u) / 256u)), 256, 0, s>>>(
+            b.summary, kSummaryWords, cc + z0, ncc, b.image ? (uint64_t)((uintptr_t)b.image - (uintptr_t)b.pool) : 0ull);
     }
     // sub_arg: sub_shift | tail quarters << 8 | largest-first rounds << 20 | item round << 22
     const uint32_t sub_arg = sub | (tq << 8) | (lpt ? kK2LptRounds << 20 | 1u << 22 : 0u);

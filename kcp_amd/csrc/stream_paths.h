@@ -55,6 +55,26 @@ GD_SP_HD inline uint32_t sp_entry_unhole(uint32_t e, uint32_t w) {
     return e + ((e >> 4) >= sp_hole_start(w) ? sp_entry(sp_hole_chunks(w), 0u) : 0u);
 }
 
+// A pair streamed from the batch's compare image (gpudiff_format.h: gpudiff_pair_image_parts) has no hole to step over:
+// its log slot carries kSpHoleImage instead, which no sp_hole_word equals (hs and hl are below 2^19 chunks together).
+// A region whose keys and metas the image dropped is  vals[L] zero padded to 16 | arena : nv = ceil(L / 2) chunks of
+// values, then the arena's.  Image chunk k is segment chunk k below nv and chunk k + (L - nv) from there on -- the
+// chunks of [8 L, 16 L) that hold no value byte are the ones left out.  With L odd, chunk nv - 1 holds the last value
+// and 8 bytes of zeros in the image, the last value and keys[0], keys[1] in the segment: its dwords 2 and 3 are zero on
+// both image sides, so a logged entry never names them and the rule above never sees a key of an imaged region.  A chunk
+// past the image part's end (the line padding) lands at or past the segment's end, where the rule refuses as before.
+constexpr uint32_t kSpHoleImage = 0xFFFFFFFFu;
+GD_SP_HD inline uint32_t sp_image_vals(uint32_t L) { return (L + 1u) >> 1; }
+GD_SP_HD inline uint32_t sp_image_chunk(uint32_t k, uint32_t L) { return k + (k >= sp_image_vals(L) ? L - sp_image_vals(L) : 0u); }
+// the compaction itself: the image chunk that holds segment chunk c of such a region, kSpRefuse for a chunk left out
+GD_SP_HD inline uint32_t sp_image_of_chunk(uint32_t c, uint32_t L) {
+    return c < sp_image_vals(L) ? c : c >= L ? c - (L - sp_image_vals(L)) : kSpRefuse;
+}
+// the entry of image chunk k as the entry of the segment's chunk
+GD_SP_HD inline uint32_t sp_entry_unimage(uint32_t e, uint32_t L) {
+    return e + ((e >> 4) >= sp_image_vals(L) ? sp_entry(L - sp_image_vals(L), 0u) : 0u);
+}
+
 // arena bytes of a leaf's value: a long string's tail past its first 8 bytes, zero padded to 4; must equal
 // gpudiff_meta_arena (include/gpudiff_format.h), restated here because K2 compiles it
 GD_SP_HD inline uint32_t sp_meta_arena(uint32_t m) {

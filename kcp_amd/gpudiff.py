@@ -35,6 +35,7 @@ OPT_PATH_STRINGS = 0x8000000  # device-encoded batches: K15/K16 render the chang
 # device-encoded batches: K21/K22 render every changed leaf's old and new value as JSON text
 # (DiffResult.path_values)
 OPT_PATH_VALUES = 0x80000000
+OPT_NO_IMAGE = 0x20  # honoured at append: no compare image for the appended pairs, their ordinary descriptors (same results)
 OPT_K2_ROWS = 0x40  # diagnostic: K2 reads the 64-B rows, not the 16-B pair descriptors (same results)
 OPT_ARENA_SHIFT = 21  # test hook: 4 bits, the K2 wave arenas shrunk 2^k-fold (forces the deferred K4 path)
 OPT_SMALL_PASS = 0x20000000  # a pass of 1..SMALL_PASS_MAX_PAIRS pairs runs as one kernel (K20) with one read-back
@@ -45,6 +46,7 @@ DEVICE_CURRENT, DEVICE_NONE = -1, -2
 PATH_HASH_BITS = 32  # GPUDIFF_PATH_HASH_BITS: segment keys and reported path hashes
 OBJ_HAS_STATUS, OBJ_DECODE_ERR, OBJ_FRESH, OBJ_SEED_SHIFT = 0x1, 0x2, 0x4, 8
 OBJ_SPEC_KEYS_EQ = 0x8  # flags_b only: both sides' spec keys[] are equal (the host encoder; K2 skips the lines of keys)
+OBJ_STAT_SHAPE_EQ = 0x20  # flags_b only: the status regions have leaves and equal keys[] and metas[] (the compare image drops them)
 OBJ_SPEC_SHAPE_EQ = 0x10  # flags_b only, beside OBJ_SPEC_KEYS_EQ: the spec metas[] are equal too (K2 skips their lines)
 STORE_DEVICE_ENCODE = 0x1
 EXPORT_COUNTS, EXPORT_SPEC_IDS, EXPORT_STATUS_IDS, EXPORT_DIRTY_IDS, EXPORT_FLAGS = range(5)
@@ -362,6 +364,10 @@ class BatchStats(C.Structure):
                 ("compare_bytes", C.c_uint64), ("value_bytes", C.c_uint64)]
 
 
+class ImageStats(C.Structure):
+    _fields_ = [("bytes_used", C.c_uint64), ("capacity", C.c_uint64), ("pairs", C.c_uint64)]
+
+
 class Timings(C.Structure):
     _fields_ = [("compare_ms", C.c_float), ("compact_ms", C.c_float),
                 ("join_ms", C.c_float), ("emit_ms", C.c_float), ("total_ms", C.c_float),
@@ -395,6 +401,9 @@ SIGNATURES = [
     ("gpudiff_shard_lpt", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     ("gpudiff_rows_stream_bytes", C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]),
     ("gpudiff_rows_read_bytes", C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]),
+    ("gpudiff_rows_image_read_bytes", C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]),
+    ("gpudiff_dbatch_set_image_capacity", C.c_int, [_P, C.c_uint64]),
+    ("gpudiff_dbatch_image_stats", C.c_int, [_P, C.POINTER(ImageStats)]),
     ("gpudiff_diff", C.c_int, [_P, _P, C.POINTER(C.c_uint64)]),
     ("gpudiff_wait", C.c_int, [_P, C.c_uint64, C.POINTER(Result)]),
     ("gpudiff_result_release", None, [_P, C.POINTER(Result)]),
@@ -588,6 +597,15 @@ def read_bytes(rows: np.ndarray) -> int:
     return int(out.value)
 
 
+def image_read_bytes(rows: np.ndarray) -> int:
+    """What K2 reads for these rows when every pair that can be is streamed from the batch's compare image
+    (gpudiff_rows_image_read_bytes); read_bytes where none is."""
+    rows = np.ascontiguousarray(rows, dtype=ROW_DTYPE)
+    out = C.c_uint64()
+    _chk(_lib.gpudiff_rows_image_read_bytes(rows.ctypes.data, rows.size, C.byref(out)), "gpudiff_rows_image_read_bytes")
+    return int(out.value)
+
+
 def shard_lpt(weights, world: int) -> np.ndarray:
     """Owner rank per cluster: greedy LPT by weight (gpudiff_shard_lpt; shard.lpt_assign restates it)."""
     w = np.ascontiguousarray(weights, dtype=np.uint64)
@@ -771,6 +789,16 @@ class DeviceBatch:
 
     def reset(self):
         _chk(_lib.gpudiff_dbatch_reset(self.engine.ctx, self.h), "gpudiff_dbatch_reset")
+
+    def set_image_capacity(self, nbytes: int):
+        """The compare image's capacity in bytes, before the first append; 0: no image
+        (gpudiff_dbatch_set_image_capacity).  Default: the pool's capacity."""
+        _chk(_lib.gpudiff_dbatch_set_image_capacity(self.h, nbytes), "gpudiff_dbatch_set_image_capacity")
+
+    def image_stats(self) -> ImageStats:
+        st = ImageStats()
+        _chk(_lib.gpudiff_dbatch_image_stats(self.h, C.byref(st)), "gpudiff_dbatch_image_stats")
+        return st
 
     def stats(self) -> BatchStats:
         st = BatchStats()

@@ -49,13 +49,15 @@ def main():
 
     # what K2 reads from the descriptors, key and shape holes out; the key holes alone out (DESIGN.md §6n's measure); the
     # same with every hole streamed
-    sb = [0, 0, 0]
+    sb = [0, 0, 0, 0]  # ... and [3]: what it reads with the compare image (a tree whose binding has it)
 
     def cpu(hb):
         if hasattr(G, "stream_bytes"):  # (a parent tree's binding may not have it)
             rows = hb.rows()
             sb[0] += G.read_bytes(rows) if hasattr(G, "read_bytes") else G.stream_bytes(rows)
             sb[2] += G.stream_bytes(rows)
+            if hasattr(G, "image_read_bytes"):
+                sb[3] += G.image_read_bytes(rows)
             rows = rows.copy()
             rows["flags_b"] &= ~np.uint32(G.OBJ_SPEC_KEYS_EQ)
             sb[1] += G.stream_bytes(rows)
@@ -82,6 +84,10 @@ def main():
     if sb[1]:
         out.update(stream_bytes=sb[0], stream_bytes_key_holes=sb[2], stream_bytes_no_holes=sb[1],
                    hole_bytes=sb[1] - sb[0])
+    if sb[3]:
+        st = db.image_stats()
+        out.update(image_read_bytes=sb[3], image_saved_bytes=sb[0] - sb[3], image_bytes_used=int(st.bytes_used),
+                   image_capacity=int(st.capacity), image_pairs=int(st.pairs))
     if parts:
         c_flags = np.concatenate([q[0] for q in parts])
         c_offs, base = [np.zeros(1, np.int64)], 0

@@ -1,7 +1,8 @@
 """The bytes K2's descriptor stream reads for the first pairs of a synthetic population, and the share its key and
 shape holes leave out (gpudiff_pair_stream_bytes, include/gpudiff_format.h), summed on the host from the product
 encoder's rows: both sums, with the key holes alone (gpudiff_rows_stream_bytes, DESIGN.md §6n's measure) and with the
-shape holes the kernel honours (gpudiff_rows_read_bytes).  No GPU needed.
+shape holes the kernel honours (gpudiff_rows_read_bytes), and what it reads when every pair that can be is streamed from
+the batch's compare image (gpudiff_rows_image_read_bytes), with and without the status shape bit.  No GPU needed.
 
     python tools/keys_hole_bytes.py --config config3 --population 200000 --pairs 100000
 """
@@ -29,7 +30,8 @@ def main():
     eng = G.Engine(device=G.DEVICE_NONE, encode_threads=args.threads)
     n = min(args.pairs, pop.n)
     out = dict(config=args.config, pairs=n, format_bytes=0, stream_bytes=0, read_bytes=0, stream_bytes_no_holes=0,
-               sizes_eq=0, keys_eq=0, shape_eq=0, pairs_with_hole=0, pairs_with_shape_hole=0)
+               sizes_eq=0, keys_eq=0, shape_eq=0, pairs_with_hole=0, pairs_with_shape_hole=0, image_read_bytes=0,
+               image_read_bytes_spec_only=0, imaged=0, imaged_stat_sized=0, imaged_stat_shape_eq=0)
     pos = 0
     while pos < n:
         m = min(65536, n - pos)
@@ -53,6 +55,16 @@ def main():
         out["shape_eq"] += int((eq & sbit).sum())
         out["pairs_with_hole"] += int((eq & bit & hole).sum())
         out["pairs_with_shape_hole"] += int((eq & sbit & shole).sum())
+        # the compare image: every spec-shape-equal pair is imaged; its status part is compacted under the status bit
+        out["image_read_bytes"] += G.image_read_bytes(rows)
+        nostat = rows.copy()
+        nostat["flags_b"] &= ~np.uint32(G.OBJ_STAT_SHAPE_EQ)
+        out["image_read_bytes_spec_only"] += G.image_read_bytes(nostat)
+        stat_sz = ((rows["flags_b"] & G.OBJ_HAS_STATUS) != 0) & (rows["stat_l_a"] == rows["stat_l_b"]) & (
+            rows["stat_ar_a"] == rows["stat_ar_b"])
+        out["imaged"] += int((eq & sbit).sum())
+        out["imaged_stat_sized"] += int((eq & sbit & stat_sz).sum())
+        out["imaged_stat_shape_eq"] += int((eq & sbit & stat_sz & ((rows["flags_b"] & G.OBJ_STAT_SHAPE_EQ) != 0)).sum())
         hb.free()
         pos += m
     out["hole_bytes"] = out["stream_bytes_no_holes"] - out["stream_bytes"]
@@ -63,6 +75,11 @@ def main():
     out["shape_hole_bytes_per_pair"] = out["shape_hole_bytes"] / n
     out["shape_hole_share"] = out["shape_hole_bytes"] / out["stream_bytes_no_holes"]
     out["read_over_stream"] = out["read_bytes"] / out["stream_bytes"]
+    out["read_bytes_per_pair"] = out["read_bytes"] / n
+    out["image_saved_bytes_per_pair"] = (out["read_bytes"] - out["image_read_bytes"]) / n
+    out["image_saved_share"] = (out["read_bytes"] - out["image_read_bytes"]) / out["read_bytes"]
+    out["image_saved_bytes_per_pair_spec_only"] = (out["read_bytes"] - out["image_read_bytes_spec_only"]) / n
+    out["image_saved_share_spec_only"] = (out["read_bytes"] - out["image_read_bytes_spec_only"]) / out["read_bytes"]
     print(json.dumps(out))
     eng.close()
     pop.close()
