@@ -345,6 +345,11 @@ typedef struct gpudiff_image_stats {
     uint64_t pairs;      /* resident pairs streamed from the image */
 } gpudiff_image_stats;
 int gpudiff_dbatch_image_stats(const gpudiff_dbatch* db, gpudiff_image_stats* st);
+/* *out = the bytes the decision kernel streams for the batch's imaged pairs in one pass: each one's 16-B descriptor and
+ * both sides' chunks of its packed parts, padded to the line as streamed.  Summed on the device by the appends' builder
+ * kernel; the call waits for the last append's builder kernel, whichever context is given (a view's will do), and reads
+ * the sum back.  0 with no image. */
+int gpudiff_dbatch_image_streamed_bytes(gpudiff_ctx* ctx, const gpudiff_dbatch* db, uint64_t* out);
 int gpudiff_dbatch_stats_get(const gpudiff_dbatch* db, gpudiff_batch_stats* st);
 int gpudiff_dbatch_device_view(const gpudiff_dbatch* db, gpudiff_device_view* v);
 /* async device-to-device copy of a diffed batch's results into caller memory
@@ -400,9 +405,16 @@ int gpudiff_rows_stream_bytes(const gpudiff_pair_row* rows, size_t n, uint64_t* 
 /* *out = the same sum with every bit honoured: what the decision kernel really reads for the rows from their
  * descriptors, key and shape holes left out (16 B + 32 B per streamed chunk, a pair) */
 int gpudiff_rows_read_bytes(const gpudiff_pair_row* rows, size_t n, uint64_t* out);
-/* *out = the sum of gpudiff_pair_image_bytes: what the decision kernel reads for the rows when every pair that can
- * be is streamed from the compare image (gpudiff_rows_read_bytes where none is) */
+/* *out = the sum of gpudiff_pair_image_bytes: what the decision kernel reads at most for the rows when every pair that
+ * can be is streamed from the compare image, each image part at its slot's size (gpudiff_rows_read_bytes where none
+ * is) */
 int gpudiff_rows_image_read_bytes(const gpudiff_pair_row* rows, size_t n, uint64_t* out);
+/* The sum above is an upper bound: an imaged pair's regions are packed to their values' true lengths
+ * (gpudiff_format.h: gpudiff_meta_packed), which takes the metas, and a row has none.  *out = what the decision kernel
+ * streams for the imaged rows alone -- 16 B + 32 B per streamed chunk of the packed parts, a pair; rows that are not
+ * imaged add nothing -- with the parts packed by A's metas in pool, the host batch's pool the rows' offsets count
+ * from.  The same sum as gpudiff_dbatch_image_streamed_bytes gives for a batch whose image held every such pair. */
+int gpudiff_rows_image_streamed_bytes(const gpudiff_pair_row* rows, size_t n, const uint8_t* pool, uint64_t* out);
 
 /* ---- diff (the hot path) ---- */
 /* enqueue K2..K6 on the context stream; returns immediately */

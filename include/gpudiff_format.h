@@ -379,16 +379,22 @@ GPUDIFF_HD static inline uint64_t gpudiff_pair_stream_bytes(const gpudiff_pair_r
 
 /* ---- the compare image (DESIGN.md §5 "Compare image"): for a row with no decode error, equal spec sizes and both
  * GPUDIFF_OBJ_SPEC_KEYS_EQ and GPUDIFF_OBJ_SPEC_SHAPE_EQ, gpudiff_dbatch_append also writes a compacted copy of what K2
- * must compare into a second allocation.  Per side, 128-B aligned, A then B:
+ * must compare into a second allocation.  Per side a 128-B aligned slot, A's then B's, sized for
  *
  *   spec vals[L] (zero padded to 16) | spec arena
  *   | the status region, when its sizes are equal and B has a status key: vals[Lt] (zero padded to 16) | status arena
  *     under GPUDIFF_OBJ_STAT_SHAPE_EQ, the whole status segment otherwise
  *   | zeros to 128
  *
- * *spec, *stat: the two parts' bytes (multiples of 16); returns 0 for a row that is not imaged (its ordinary descriptor
- * is the escape, or its image spec part would not leave the mark free).  Chunk k of a part whose keys and metas were
- * dropped is chunk k of the segment below ceil(L / 2) and chunk k + L - ceil(L / 2) from there on (stream_paths.h). */
+ * A part whose keys and metas are dropped is written packed to its values' true lengths (gpudiff_meta_packed, below) at
+ * the slot's front, the next part and the zeros to the line right behind it: the slot keeps the size above, the bytes
+ * behind a packed side are neither written nor streamed, and the pair's descriptor carries the packed parts' sizes.
+ *
+ * *spec, *stat: the two parts' slot bytes (multiples of 16); returns 0 for a row that is not imaged (its ordinary descriptor
+ * is the escape, or its image spec part would not leave the mark free).  (stream_paths.h's sp_image_vals /
+ * sp_image_chunk / sp_entry_unimage -- chunk k of a compacted part as chunk k of the segment below ceil(L / 2), chunk
+ * k + L - ceil(L / 2) from there on -- are the slot-size arithmetic of this layout and nothing else now: a packed part's
+ * chunks are not mapped back to the segment, and only tests/test_image_rule.py calls them.) */
 GPUDIFF_HD static inline int gpudiff_pair_image_parts(const gpudiff_pair_row* r, uint32_t* spec, uint32_t* stat) {
     const uint32_t need = GPUDIFF_OBJ_SPEC_KEYS_EQ | GPUDIFF_OBJ_SPEC_SHAPE_EQ;
     *spec = *stat = 0u;
@@ -414,20 +420,23 @@ GPUDIFF_HD static inline uint64_t gpudiff_pair_image_side(const gpudiff_pair_row
     if (!gpudiff_pair_image_parts(r, &s, &t)) return 0u;
     return ((uint64_t)s + t + (GPUDIFF_BLOB_ALIGN - 1u)) & ~(uint64_t)(GPUDIFF_BLOB_ALIGN - 1u);
 }
-/* the image form of the row's descriptor, its sides at bytes img_a and img_b of the image; the escape (K2 then reads
- * the row and the pool) when the row is not imaged or an offset does not fit */
-GPUDIFF_HD static inline gpudiff_pair_desc gpudiff_pair_desc_pack_image(const gpudiff_pair_row* r, uint64_t img_a,
-                                                                        uint64_t img_b) {
+/* the image form of the row's descriptor, its sides at bytes img_a and img_b of the image, with the two parts' bytes as
+ * streamed given (multiples of 16, at most gpudiff_pair_image_parts': a packed part, below, is shorter than its slot);
+ * the escape (K2 then reads the row and the pool) when the row is not imaged or an offset does not fit */
+GPUDIFF_HD static inline gpudiff_pair_desc gpudiff_pair_desc_pack_image_parts(const gpudiff_pair_row* r, uint32_t spec,
+                                                                              uint32_t stat, uint64_t img_a,
+                                                                              uint64_t img_b) {
     gpudiff_pair_desc d;
     uint32_t s, t;
-    if (!gpudiff_pair_image_parts(r, &s, &t) || ((img_a | img_b) & (GPUDIFF_BLOB_ALIGN - 1u)) != 0u ||
-        (img_a >> 7) > 0xFFFFFFFFull || (img_b >> 7) > 0xFFFFFFFFull) {
+    if (!gpudiff_pair_image_parts(r, &s, &t) || spec > s || stat > t || ((spec | stat) & 15u) != 0u ||
+        ((img_a | img_b) & (GPUDIFF_BLOB_ALIGN - 1u)) != 0u || (img_a >> 7) > 0xFFFFFFFFull ||
+        (img_b >> 7) > 0xFFFFFFFFull) {
         d.w[0] = d.w[1] = d.w[2] = d.w[3] = GPUDIFF_PD_ESCAPE;
         return d;
     }
     {
-        const uint64_t zw = (uint64_t)(s >> 4) | ((uint64_t)GPUDIFF_PD_SIZE_MAX << GPUDIFF_PD_SIZE_BITS) |
-                            ((uint64_t)(t >> 4) << (2u * GPUDIFF_PD_SIZE_BITS)) |
+        const uint64_t zw = (uint64_t)(spec >> 4) | ((uint64_t)GPUDIFF_PD_SIZE_MAX << GPUDIFF_PD_SIZE_BITS) |
+                            ((uint64_t)(stat >> 4) << (2u * GPUDIFF_PD_SIZE_BITS)) |
                             ((uint64_t)gpudiff_pair_row_bits(r) << (3u * GPUDIFF_PD_SIZE_BITS));
         d.w[0] = (uint32_t)(img_a >> 7);
         d.w[1] = (uint32_t)(img_b >> 7);
@@ -436,8 +445,17 @@ GPUDIFF_HD static inline gpudiff_pair_desc gpudiff_pair_desc_pack_image(const gp
     }
     return d;
 }
-/* the bytes the descriptor kernel reads for one pair of a batch that images every row it can: the descriptor and both
- * image sides' streamed chunks; gpudiff_pair_stream_bytes for a row that is not imaged */
+/* ... with the parts at their slots' sizes (gpudiff_pair_image_parts): the row's own arithmetic, no meta read */
+GPUDIFF_HD static inline gpudiff_pair_desc gpudiff_pair_desc_pack_image(const gpudiff_pair_row* r, uint64_t img_a,
+                                                                        uint64_t img_b) {
+    uint32_t s = 0, t = 0;
+    (void)gpudiff_pair_image_parts(r, &s, &t); /* (not imaged: the variant finds out again and escapes) */
+    return gpudiff_pair_desc_pack_image_parts(r, s, t, img_a, img_b);
+}
+/* an upper bound on the bytes the descriptor kernel reads for one pair of a batch that images every row it can: the
+ * descriptor and both image sides' chunks at the slots' sizes (packed parts are shorter, but their sizes take the metas
+ * and a row has none: gpudiff_rows_image_streamed_bytes, gpudiff.h); gpudiff_pair_stream_bytes for a row that is not
+ * imaged */
 GPUDIFF_HD static inline uint64_t gpudiff_pair_image_bytes(const gpudiff_pair_row* r) {
     const gpudiff_pair_desc d = gpudiff_pair_desc_pack_image(r, 0u, 0u);
     if (gpudiff_pair_desc_is_escape(d.w[3])) return gpudiff_pair_stream_bytes(r);
@@ -461,6 +479,46 @@ GPUDIFF_HD static inline uint32_t gpudiff_meta_arena(uint32_t m) {
 /* a segment's arena size (the row's *_ar fields): the sum of its leaves'
  * gpudiff_meta_arena, rounded up to 16 */
 GPUDIFF_HD static inline uint32_t gpudiff_arena_bytes(uint32_t sum) { return (sum + 15u) & ~15u; }
+
+/* ---- the packed region (DESIGN.md §5 "Compare image"): what the image keeps of a region whose keys and metas it drops
+ * -- the spec region of every imaged pair, the status region under GPUDIFF_OBJ_STAT_SHAPE_EQ.  The leaves in key order,
+ * leaf i taking gpudiff_meta_packed(m_i) bytes, then zeros to a multiple of 16:
+ *
+ *   string          its length rounded up to 4: the first min(len, 8) bytes from vals[i], the rest its arena tail (which
+ *                   is zero padded to 4 already; a string of at most 8 bytes takes pad4(len) bytes of its vals slot)
+ *   int64, float64  the 8 bytes of vals[i]
+ *   null, false, true, {}, []   nothing: the meta is the value, and vals[i] is 8 zero bytes by the format
+ *
+ * Under equal metas leaf i lies at the same packed offset on both sides and the packed bytes hold every byte of its
+ * value, so two packed regions are equal iff the regions' values are.  Never longer than vals[L] padded to 16 plus the
+ * arena: a leaf takes at most its 8 bytes of vals and its tail. */
+GPUDIFF_HD static inline uint32_t gpudiff_meta_packed(uint32_t m) {
+    const uint32_t tag = gpudiff_meta_tag(m);
+    if (tag == GPUDIFF_TAG_STR) return (gpudiff_meta_len(m) + 3u) & ~3u;
+    return (tag == GPUDIFF_TAG_INT || tag == GPUDIFF_TAG_FLOAT) ? 8u : 0u;
+}
+/* a packed region's bytes: the sum of its leaves' gpudiff_meta_packed, rounded up to 16 */
+GPUDIFF_HD static inline uint32_t gpudiff_packed_bytes(uint32_t sum) { return (sum + 15u) & ~15u; }
+/* the same from a region's metas[L] */
+GPUDIFF_HD static inline uint32_t gpudiff_region_packed_bytes(const uint32_t* metas, uint32_t l) {
+    uint32_t sum = 0, i;
+    for (i = 0; i < l; i++) sum += gpudiff_meta_packed(metas[i]);
+    return gpudiff_packed_bytes(sum);
+}
+/* the packing itself, serially (the builder kernel does the same a wave per pair): seg the region's segment on the
+ * side to pack, metas the metas that say how (A's, for both sides), dst gpudiff_region_packed_bytes(metas, l) bytes */
+GPUDIFF_HD static inline uint32_t gpudiff_region_pack(const uint8_t* seg, const uint32_t* metas, uint32_t l, uint8_t* dst) {
+    const uint8_t* arena = seg + 16ull * l;
+    uint32_t p = 0, t = 0, i, k;
+    for (i = 0; i < l; i++) {
+        const uint32_t n = gpudiff_meta_packed(metas[i]), ar = gpudiff_meta_arena(metas[i]);
+        for (k = 0; k < n; k++) dst[p + k] = k < 8u ? seg[8ull * i + k] : arena[t + (k - 8u)];
+        p += n;
+        t += ar;
+    }
+    for (; p & 15u; p++) dst[p] = 0u;
+    return p;
+}
 
 #ifdef __cplusplus
 }

@@ -1109,6 +1109,16 @@ func RowsImageReadBytes(rows unsafe.Pointer, n int) (uint64, error) {
 	return uint64(out), nil
 }
 
+// RowsImageStreamedBytes sums what the decision kernel streams for the imaged pairs among n pair rows, their parts
+// packed by A's metas in pool, the host batch's pool the rows' offsets count from (gpudiff_rows_image_streamed_bytes).
+func RowsImageStreamedBytes(rows unsafe.Pointer, n int, pool unsafe.Pointer) (uint64, error) {
+	var out C.uint64_t
+	if err := errOf(C.gpudiff_rows_image_streamed_bytes((*C.gpudiff_pair_row)(rows), C.size_t(n), (*C.uint8_t)(pool), &out)); err != nil {
+		return 0, err
+	}
+	return uint64(out), nil
+}
+
 // RowsReadBytes sums what the decision kernel reads for n pair rows (gpudiff_pair_row, 64 bytes each) from their
 // descriptors, key and shape holes left out (gpudiff_rows_read_bytes).  For measurements; the shard weight stays the
 // format's bytes.

@@ -477,6 +477,17 @@ static bool image_ready(gpudiff_ctx* c, gpudiff_dbatch* d, uint64_t n) {
             d->image_off = true;
             return false;
         }
+        if (hipMalloc((void**)&d->image_streamed, sizeof(uint64_t)) != hipSuccess ||
+            hipMemsetAsync(d->image_streamed, 0, sizeof(uint64_t), c->stream) != hipSuccess ||
+            hipEventCreateWithFlags(&d->image_built, hipEventDisableTiming) != hipSuccess) {
+            (void)hipGetLastError();
+            if (d->image_streamed) (void)hipFree(d->image_streamed);
+            if (d->image_built) (void)hipEventDestroy(d->image_built);
+            (void)hipFree(d->image);
+            d->image = nullptr, d->image_streamed = nullptr, d->image_built = nullptr;
+            d->image_off = true;
+            return false;
+        }
         d->image_cap = cap;
     }
     if (n > d->image_scan_n) {
@@ -514,6 +525,44 @@ int gpudiff_dbatch_image_stats(const gpudiff_dbatch* d, gpudiff_image_stats* st)
     return GPUDIFF_OK;
 }
 
+int gpudiff_dbatch_image_streamed_bytes(gpudiff_ctx* c, const gpudiff_dbatch* d, uint64_t* out) {
+    if (!c || !d || !out) return GPUDIFF_E_INVAL;
+    if (d->base) d = d->base;
+    *out = 0;
+    if (!d->image_streamed) return GPUDIFF_OK;  // no image: nothing is streamed from one
+    int rc = set_device(c);
+    if (rc) return rc;
+    // the last append's builder kernel, whichever context appended and whichever asks (a view's: its own stream
+    // knows nothing of the base's appends)
+    HIPCHK(hipEventSynchronize(d->image_built));
+    HIPCHK(hipMemcpy(out, d->image_streamed, sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return GPUDIFF_OK;
+}
+
+// what the builder sums on the device, from a host batch's rows and pool: each imaged row's descriptor and both sides'
+// chunks, the parts packed by A's metas in the pool (gpudiff_region_packed_bytes)
+int gpudiff_rows_image_streamed_bytes(const gpudiff_pair_row* rows, size_t n, const uint8_t* pool, uint64_t* out) {
+    if ((!rows && n) || (!pool && n) || !out) return GPUDIFF_E_INVAL;
+    uint64_t sum = 0;
+    for (size_t i = 0; i < n; i++) {
+        const gpudiff_pair_row& r = rows[i];
+        uint32_t s = 0, t = 0;
+        if (!gpudiff_pair_image_parts(&r, &s, &t)) continue;
+        const uint8_t* a = pool + r.off_a;
+        const uint64_t seg_s = gpudiff_seg_bytes(r.spec_l_a, r.spec_ar_a);
+        const uint32_t sp = gpudiff_region_packed_bytes((const uint32_t*)(a + 12ull * r.spec_l_a), r.spec_l_a);
+        const uint32_t tp = (t && (r.flags_b & GPUDIFF_OBJ_STAT_SHAPE_EQ))
+                                ? gpudiff_region_packed_bytes((const uint32_t*)(a + seg_s + 12ull * r.stat_l_a), r.stat_l_a)
+                                : t;
+        const gpudiff_pair_desc d = gpudiff_pair_desc_pack_image_parts(&r, sp, tp, 0u, 0u);
+        if (gpudiff_pair_desc_is_escape(d.w[3])) continue;
+        const gpudiff_pair_geom g = gpudiff_pair_desc_unpack(d.w[0], d.w[1], d.w[2], d.w[3]);
+        sum += sizeof(gpudiff_pair_desc) + 32ull * ((uint64_t)g.n1 + g.n2);
+    }
+    *out = sum;
+    return GPUDIFF_OK;
+}
+
 int gpudiff_dbatch_append(gpudiff_ctx* c, gpudiff_dbatch* d, const gpudiff_hbatch* hb) {
     if (!c || !d || !hb || d->base) return GPUDIFF_E_INVAL;
     int rc = set_device(c);
@@ -529,9 +578,11 @@ int gpudiff_dbatch_append(gpudiff_ctx* c, gpudiff_dbatch* d, const gpudiff_hbatc
     if (hb->used) HIPCHK(hipEventRecord(hb->used, c->stream));
     HIPCHK(launch_rebase(c->stream, d->rows, begin, end, base, d->pair_ids, d->desc));
     const bool imaging = image_ready(c, d, hb->n);
-    if (imaging)
+    if (imaging) {
         HIPCHK(launch_image_build(c->stream, d->rows, begin, end, d->image_scan, d->image_cursor, d->image_cap, d->pool,
-                                  d->image, d->desc));
+                                  d->image, d->desc, d->image_streamed));
+        HIPCHK(hipEventRecord(d->image_built, c->stream));
+    }
     uint64_t cb = 0, vb = 0;
     for (size_t i = 0; i < hb->n; i++) {
         const gpudiff_pair_row& r = hb->rows[i];
@@ -566,6 +617,7 @@ int gpudiff_dbatch_reset(gpudiff_ctx* c, gpudiff_dbatch* d) {
     HIPCHK(hipStreamSynchronize(c->stream));
     d->pool_used = d->n_pairs = d->leaves = d->compare_bytes = d->value_bytes = d->size_hint_bytes = 0;
     d->image_cursor = d->image_used = d->image_pairs = 0;
+    if (d->image_streamed) HIPCHK(hipMemset(d->image_streamed, 0, sizeof(uint64_t)));
     d->ticket = 0;
     d->rows_gen++;
     return GPUDIFF_OK;

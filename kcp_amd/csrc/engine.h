@@ -149,6 +149,10 @@ struct gpudiff_dbatch {
     bool image_off = false;
     uint64_t* image_scan = nullptr;
     uint64_t image_scan_n = 0;
+    // what K2 streams of the imaged pairs (their descriptors and packed chunks), summed by the builder on the device:
+    // one u64 allocated with the image, read back by gpudiff_dbatch_image_streamed_bytes
+    uint64_t* image_streamed = nullptr;
+    hipEvent_t image_built = nullptr;  // recorded behind each append's builder kernel: the sum's reader waits for it
     // GPUDIFF_OPT_SMALL_PASS: the result image K20 packs (small_pass.h; allocated by the batch's first small pass),
     // and whether the pass `done` stands for was a small one (collect_results reads the image then)
     uint8_t* small_image = nullptr;
@@ -314,7 +318,10 @@ inline void dfree_all(gpudiff_dbatch* d) {
     if (d->base) d->rows = nullptr, d->pair_ids = nullptr, d->desc = nullptr, d->image = nullptr;  // a view's inputs are its base's
     if (d->image) (void)hipFree(d->image);
     if (d->image_scan) (void)hipFree(d->image_scan);
-    d->image = nullptr, d->image_scan = nullptr;
+    if (d->image_streamed) (void)hipFree(d->image_streamed);
+    if (d->image_built) (void)hipEventDestroy(d->image_built);
+    d->image_built = nullptr;
+    d->image = nullptr, d->image_scan = nullptr, d->image_streamed = nullptr;
     void* ps[] = {d->rows, d->pair_ids, d->desc, d->flags, d->caps, d->chunk_counts, d->summary, d->spec_ids,
                   d->status_ids, d->dirty_ids, d->dirty_idx, d->scratch_off, d->path_count, d->path_off,
                   d->tile_sums, d->path_src, d->path_cnt, d->arena_h, d->arena_k,

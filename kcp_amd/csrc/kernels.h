@@ -94,10 +94,12 @@ hipError_t launch_rebase(hipStream_t s, gpudiff_pair_row* rows, uint32_t begin, 
                          uint32_t* pair_ids, uint4* desc);
 // The compare image of the appended rows [begin, end), after launch_rebase: each imaged pair's sides into `image` from
 // byte `used` on (an exclusive sum of the chunk's image bytes) and its descriptor replaced by the image form; a pair
-// that would end past cap keeps its descriptor.  scan: image_scan_words(end - begin) u64 of device scratch.
+// that would end past cap keeps its descriptor.  scan: image_scan_words(end - begin) u64 of device scratch.  *streamed
+// (device) grows by the bytes K2 reads of the pairs imaged here.
 inline uint64_t image_scan_words(uint32_t n) { return 2ull * n + 2u + (n + 1023u) / 1024u; }
 hipError_t launch_image_build(hipStream_t s, const gpudiff_pair_row* rows, uint32_t begin, uint32_t end, uint64_t* scan,
-                              uint64_t used, uint64_t cap, const uint8_t* pool, uint8_t* image, uint4* desc);
+                              uint64_t used, uint64_t cap, const uint8_t* pool, uint8_t* image, uint4* desc,
+                              uint64_t* streamed);
 // object-store compaction: blob copies between the two spaces
 struct BlobMove {
     uint64_t src, dst, bytes;

@@ -160,9 +160,11 @@ struct StreamLog {
 // lane per differing dword, then a lane per changed leaf): written where join_region<true> would write them, in
 // its order (ascending leaf = ascending key), with its *weq_all.  Returns the path count, or kSpRefuse with
 // nothing written that the join does not overwrite: the caller then joins the region.
-// IMG (the descriptor kernel): hole may be kSpHoleImage -- the region streamed from the compare image without its keys
-// and metas, so a logged chunk goes back to the segment through sp_entry_unimage; A, B stay the pool's views (every
-// gather below and the join read the pool, never the image).
+// IMG (the descriptor kernel): hole may be kSpHoleImage -- the region streamed from the compare image, packed
+// (stream_paths.h: sp_packed_rule): a logged dword is a value dword of the leaf whose packed bytes hold it, found by
+// the same window search over sp_pk of A's metas that finds an arena dword's owner over meta_arena, and a byte past
+// the last leaf's is the final padding.  A, B stay the pool's views (every gather below and the join read the pool,
+// never the image).
 template <bool IMG>
 __device__ uint32_t stream_region(const RegionView& A, const RegionView& B, uint64_t seg, const uint32_t* ent,
                                   uint32_t c, uint32_t g0, uint32_t hole, uint8_t region_bit,
@@ -171,15 +173,16 @@ __device__ uint32_t stream_region(const RegionView& A, const RegionView& B, uint
     const uint32_t nc = 4u * c;  // <= 16 candidate lanes: dword (lane & 3) of entry (lane >> 2)
     // g0: the region's first chunk; hole: the streamed index back to the chunk's place in the segment
     uint32_t e = 0u;
+    const bool packed = IMG && hole == kSpHoleImage;  // (wave-uniform)
     if (lane < nc) {
         const uint32_t e0 = ent[lane >> 2] - sp_entry(g0, 0u);
-        if (IMG && hole == kSpHoleImage) e = sp_entry_unimage(e0, A.L);
-        else e = sp_entry_unhole(e0, hole);
+        e = packed ? e0 : sp_entry_unhole(e0, hole);
     }
     const bool cand = lane < nc && ((sp_entry_dwords(e) >> (lane & 3u)) & 1u);
     const uint64_t b = sp_entry_byte(e, lane & 3u);
-    const SpWhere w = sp_classify(b, A.L);
-    if (ballot(cand && (b >= seg || w.cls == SP_KEY))) return kSpRefuse;
+    // (a packed region: every dword is searched for by its packed byte, as an arena dword is by its arena byte)
+    const SpWhere w = packed ? SpWhere{SP_ARENA, (uint32_t)b} : sp_classify(b, A.L);
+    if (ballot(cand && !packed && (b >= seg || w.cls == SP_KEY))) return kSpRefuse;
     uint32_t leaf = w.idx;
     const bool ar = cand && w.cls == SP_ARENA;
     if (ballot(ar)) {  // the owners of the arena dwords: the prefix sum of side A's tail sizes, 64 leaves a step
@@ -187,7 +190,8 @@ __device__ uint32_t stream_region(const RegionView& A, const RegionView& B, uint
         uint32_t run = 0;
         for (uint32_t i0 = 0; i0 < A.L; i0 += 64u) {
             const uint32_t n = min(64u, A.L - i0);
-            const uint32_t as = lane < n ? meta_arena(A.metas[i0 + lane]) : 0u;
+            const uint32_t as =
+                lane < n ? (packed ? sp_pk(A.metas[i0 + lane]) : meta_arena(A.metas[i0 + lane])) : 0u;
             const uint32_t inc = wave_incl_scan(as);
             const uint32_t tot = shfl32(inc, 63);
             const uint32_t rel = w.idx - run;
@@ -202,7 +206,7 @@ __device__ uint32_t stream_region(const RegionView& A, const RegionView& B, uint
             run += tot;
             if (!ballot(ar && !found)) break;
         }
-        if (ballot(ar && !found)) return kSpRefuse;  // the arena's final padding
+        if (ballot(ar && !found)) return kSpRefuse;  // the arena's, or the packed region's, final padding
     }
     // S: the distinct leaves, ranked ascending
     bool dup = false;
@@ -239,9 +243,9 @@ __device__ uint32_t stream_region(const RegionView& A, const RegionView& B, uint
 
 // join_pair<true> for K2's own pairs: a size-matched region the stream found dirty is emitted from the wave's
 // log when the rule allows (*n_stream counts those), joined otherwise; spec, status, sentinel as in join_pair.
-// IMG: a pair streamed from the compare image (its log slot's hole is kSpHoleImage) maps its spec chunks back with
-// spec_l, and its status chunks with stat_l when the row carries GPUDIFF_OBJ_STAT_SHAPE_EQ (the image then holds the
-// status vals and arena alone; otherwise the status segment was copied whole and its chunks are the segment's)
+// IMG: a pair streamed from the compare image (its log slot's hole is kSpHoleImage) has its spec region packed, and
+// its status region when the row carries GPUDIFF_OBJ_STAT_SHAPE_EQ (otherwise the status segment was copied whole and
+// its chunks are the segment's)
 template <bool IMG>
 __device__ uint32_t stream_pair(const gpudiff_pair_row& r, uint32_t f, const uint8_t* pool, uint64_t mask,
                                 uint64_t* out_h, uint8_t* out_k, uint32_t base, uint32_t lane, uint32_t* noop,
@@ -1371,16 +1375,62 @@ __global__ __launch_bounds__(256) void k_image_sizes(const gpudiff_pair_row* __r
     const gpudiff_pair_row r = rows[i];
     sizes[i - begin] = 2ull * gpudiff_pair_image_side(&r);
 }
-// ... then a wave per pair copies the 16-B chunks the image keeps, A's side then B's, each zero padded to the line, and
-// replaces the pair's descriptor by the image form.  offsets[i - begin]: the pair's place after `used` (the image
-// bytes of the appends before).  A pair that would end past cap keeps the descriptor k_rebase_rows wrote; so does
-// every later one, since the offsets only grow.
+// One region of one side into the image, packed (gpudiff_format.h: gpudiff_region_pack, here a wave at it): seg the
+// side's segment, metas side A's metas of the region (equal to this side's by the row's bits), ar its arena bytes, dst
+// the part's first byte, lim the bytes of its slot.  A leaf a lane in rounds of 64: the exclusive sums of sp_pk and of
+// meta_arena place each leaf's packed bytes and its tail; the lane stores its leaf's head (at most 8 bytes of vals), and
+// the round's tails -- contiguous in the arena -- are copied a dword a lane, each dword finding its leaf in the round's
+// sums.  Returns the packed bytes (a multiple of 16, wave-uniform); stores nothing past lim and loads nothing past the
+// arena, so metas that contradict the row's sizes (never an encoder's) return more than lim and harm nothing.
+__device__ uint32_t image_pack_region(const uint8_t* __restrict__ seg, const uint32_t* __restrict__ metas, uint32_t L,
+                                      uint32_t ar, uint32_t* __restrict__ dst, uint32_t lim, uint32_t lane) {
+    const uint32_t* vals = (const uint32_t*)seg;
+    const uint32_t* arena = (const uint32_t*)(seg + 16ull * L);
+    uint32_t pb = 0, tb = 0;  // packed and tail bytes of the rounds before (wave-uniform)
+    for (uint32_t i0 = 0; i0 < L; i0 += 64u) {
+        const uint32_t n = min(64u, L - i0);
+        const uint32_t m = lane < n ? metas[i0 + lane] : 0u;  // (0: a null, no byte either way)
+        const uint32_t pk = sp_pk(m), tl = meta_arena(m);
+        const uint32_t pin = wave_incl_scan(pk), tin = wave_incl_scan(tl);
+        const uint32_t ptot = uni(shfl32(pin, 63)), ttot = uni(shfl32(tin, 63));
+        const uint32_t P = pb + pin - pk, tex = tin - tl;  // the leaf's packed offset; its tail's in the round's tails
+        if (pk && P <= lim && min(pk, 8u) <= lim - P) {
+            dst[P >> 2] = vals[2u * (i0 + lane)];
+            if (pk > 4u) dst[(P >> 2) + 1u] = vals[2u * (i0 + lane) + 1u];
+        }
+        for (uint32_t w0 = 0; w0 < ttot; w0 += 256u) {  // (uniform trips: every lane serves the reads below)
+            const uint32_t w = w0 + 4u * lane;
+            uint32_t o = 0;  // the round's leaves whose tails end at or before byte w
+#pragma unroll
+            for (uint32_t st = 32; st >= 1; st >>= 1)
+                if (shfl32(tin, o + st - 1u) <= w) o += st;
+            const uint32_t Po = shfl32(P, o & 63u), to = shfl32(tex, o & 63u);
+            const uint32_t at = Po + 8u + (w - to);  // then tin[o] > w: leaf o's tail holds the byte
+            if (w < ttot && tb + w < ar && at < lim) dst[at >> 2] = arena[(tb + w) >> 2];
+        }
+        pb += ptot;
+        tb += ttot;
+    }
+    const uint32_t end = (pb + 15u) & ~15u;
+    if (pb + 4u * lane < end && end <= lim) dst[(pb >> 2) + lane] = 0u;
+    return end;
+}
+
+// ... then a wave per pair writes what the image keeps, A's side then B's, each to the front of its 128-B aligned slot:
+// the spec region packed by A's metas, the status region packed too under GPUDIFF_OBJ_STAT_SHAPE_EQ and copied whole
+// otherwise, zeros to the line.  The slot keeps gpudiff_pair_image_side bytes; what lies behind the packed side is
+// neither written nor streamed.  The pair's descriptor becomes the image form with the packed parts' sizes.
+// offsets[i - begin]: the pair's place after `used` (the image bytes of the appends before).  A pair that would end past
+// cap keeps the descriptor k_rebase_rows wrote; so does every later one, since the offsets only grow.  *streamed grows
+// by what K2 reads of each pair imaged here (its descriptor and both sides' chunks).
 __global__ __launch_bounds__(256) void k_image_build(const gpudiff_pair_row* __restrict__ rows, uint32_t begin,
                                                      uint32_t end, const uint64_t* __restrict__ offsets, uint64_t used,
                                                      uint64_t cap, const uint8_t* __restrict__ pool,
-                                                     uint8_t* __restrict__ image, uint4* __restrict__ desc) {
+                                                     uint8_t* __restrict__ image, uint4* __restrict__ desc,
+                                                     unsigned long long* __restrict__ streamed) {
     const uint32_t lane = lane_id();
     const uint32_t nw = (gridDim.x * blockDim.x) >> 6;
+    uint64_t sum = 0;  // (wave-uniform)
     for (uint32_t p = begin + uni((blockIdx.x * blockDim.x + threadIdx.x) >> 6); p < end; p += nw) {
         const gpudiff_pair_row r = rows[p];
         uint32_t s = 0, t = 0;
@@ -1388,32 +1438,35 @@ __global__ __launch_bounds__(256) void k_image_build(const gpudiff_pair_row* __r
         const uint64_t side = ((uint64_t)s + t + 127u) & ~127ull;
         const uint64_t o = used + offsets[p - begin];
         if (o + 2u * side > cap) continue;
-        const uint32_t nv = sp_image_vals(r.spec_l_a), drop = r.spec_l_a - nv;
         const bool tsh = t != 0u && (r.flags_b & GPUDIFF_OBJ_STAT_SHAPE_EQ) != 0u;
-        const uint32_t nvt = sp_image_vals(r.stat_l_a), tdrop = tsh ? r.stat_l_a - nvt : 0u;
-        const uint32_t cs = s >> 4, ct = t >> 4, cside = (uint32_t)(side >> 4);
-        const uint32_t seg_c = (uint32_t)(seg_bytes(r.spec_l_a, r.spec_ar_a) >> 4);  // the status segment's first chunk
+        const uint64_t seg_s = seg_bytes(r.spec_l_a, r.spec_ar_a);  // the status segment's first byte
+        const uint32_t* const ms = (const uint32_t*)(pool + r.off_a + 12ull * r.spec_l_a);
+        const uint32_t* const mt = (const uint32_t*)(pool + r.off_a + seg_s + 12ull * r.stat_l_a);
+        uint32_t sp = 0, tp = 0;
         for (uint32_t x = 0; x < 2u; x++) {
-            const u32x4* src = (const u32x4*)(pool + (x ? r.off_b : r.off_a));
-            u32x4* dst = (u32x4*)(image + o + x * side);
-            for (uint32_t q = lane; q < cside; q += 64u) {
-                u32x4 v = {0u, 0u, 0u, 0u};
-                if (q < cs) {
-                    v = src[q < nv ? q : q + drop];
-                    if ((r.spec_l_a & 1u) && q == nv - 1u) v.z = v.w = 0u;  // keys[0], keys[1] beside the last value
-                } else if (q - cs < ct) {
-                    const uint32_t k = q - cs;
-                    v = src[seg_c + ((tsh && k >= nvt) ? k + tdrop : k)];
-                    if (tsh && (r.stat_l_a & 1u) && k == nvt - 1u) v.z = v.w = 0u;
-                }
-                dst[q] = v;
+            const uint8_t* src = pool + (x ? r.off_b : r.off_a);
+            uint8_t* dst = image + o + x * side;
+            sp = image_pack_region(src, ms, r.spec_l_a, r.spec_ar_a, (uint32_t*)dst, s, lane);
+            if (sp > s) break;
+            tp = t;
+            if (tsh) {
+                tp = image_pack_region(src + seg_s, mt, r.stat_l_a, r.stat_ar_a, (uint32_t*)(dst + sp), t, lane);
+                if (tp > t) break;
+            } else {
+                for (uint32_t q = lane; q < (t >> 4); q += 64u)
+                    ((u32x4*)(dst + sp))[q] = ((const u32x4*)(src + seg_s))[q];
             }
+            const uint32_t e = sp + tp;  // (<= s + t: the zeros stay inside the slot)
+            if (lane < (((e + 127u) & ~127u) - e) >> 4) ((u32x4*)(dst + e))[lane] = u32x4{0u, 0u, 0u, 0u};
         }
-        if (lane == 0) {
-            const gpudiff_pair_desc d = gpudiff_pair_desc_pack_image(&r, o, o + side);
-            if (!gpudiff_pair_desc_is_escape(d.w[3])) desc[p] = make_uint4(d.w[0], d.w[1], d.w[2], d.w[3]);
-        }
+        if (sp > s || tp > t) continue;
+        const gpudiff_pair_desc d = gpudiff_pair_desc_pack_image_parts(&r, sp, tp, o, o + side);
+        if (gpudiff_pair_desc_is_escape(d.w[3])) continue;
+        if (lane == 0) desc[p] = make_uint4(d.w[0], d.w[1], d.w[2], d.w[3]);
+        const gpudiff_pair_geom g = gpudiff_pair_desc_unpack(d.w[0], d.w[1], d.w[2], d.w[3]);
+        sum += sizeof(gpudiff_pair_desc) + 32ull * ((uint64_t)g.n1 + g.n2);
     }
+    if (lane == 0 && sum) atomicAdd(streamed, (unsigned long long)sum);
 }
 
 // ---------------------------------------------------------------- launchers
@@ -1436,7 +1489,8 @@ hipError_t launch_rebase(hipStream_t s, gpudiff_pair_row* rows, uint32_t begin, 
 
 
 hipError_t launch_image_build(hipStream_t s, const gpudiff_pair_row* rows, uint32_t begin, uint32_t end, uint64_t* scan,
-                              uint64_t used, uint64_t cap, const uint8_t* pool, uint8_t* image, uint4* desc) {
+                              uint64_t used, uint64_t cap, const uint8_t* pool, uint8_t* image, uint4* desc,
+                              uint64_t* streamed) {
     if (end <= begin) return hipSuccess;
     const uint32_t n = end - begin;
     // scan: sizes[n] | offsets[n + 1] | tile sums | total (image_scan_words(n) u64)
@@ -1449,7 +1503,8 @@ hipError_t launch_image_build(hipStream_t s, const gpudiff_pair_row* rows, uint3
     if (e != hipSuccess) return e;
     if ((e = launch_scan64_sums(s, sizes, n, tiles, total)) != hipSuccess) return e;
     if ((e = launch_scan64_offsets(s, sizes, n, tiles, offsets)) != hipSuccess) return e;
-    k_image_build<<<grid_for(n, kPersistBlocks), 256, 0, s>>>(rows, begin, end, offsets, used, cap, pool, image, desc);
+    k_image_build<<<grid_for(n, kPersistBlocks), 256, 0, s>>>(rows, begin, end, offsets, used, cap, pool, image, desc,
+                                                              (unsigned long long*)streamed);
     return hipGetLastError();
 }
 

@@ -57,7 +57,9 @@ GD_SP_HD inline uint32_t sp_entry_unhole(uint32_t e, uint32_t w) {
 
 // A pair streamed from the batch's compare image (gpudiff_format.h: gpudiff_pair_image_parts) has no hole to step over:
 // its log slot carries kSpHoleImage instead, which no sp_hole_word equals (hs and hl are below 2^19 chunks together).
-// A region whose keys and metas the image dropped is  vals[L] zero padded to 16 | arena : nv = ceil(L / 2) chunks of
+// A region whose keys and metas the image drops is written packed (sp_packed_rule, at the end) into a slot that keeps the
+// size of the chunk compaction described next -- the slot's accounting (gpudiff_pair_image_parts) and
+// tests/test_image_rule.py hold it: the region as  vals[L] zero padded to 16 | arena : nv = ceil(L / 2) chunks of
 // values, then the arena's.  Image chunk k is segment chunk k below nv and chunk k + (L - nv) from there on -- the
 // chunks of [8 L, 16 L) that hold no value byte are the ones left out.  With L odd, chunk nv - 1 holds the last value
 // and 8 bytes of zeros in the image, the last value and keys[0], keys[1] in the segment: its dwords 2 and 3 are zero on
@@ -80,6 +82,14 @@ GD_SP_HD inline uint32_t sp_entry_unimage(uint32_t e, uint32_t L) {
 GD_SP_HD inline uint32_t sp_meta_arena(uint32_t m) {
     return ((m & 7u) == GPUDIFF_TAG_STR && (m >> 3) > GPUDIFF_INLINE_MAX) ? (((m >> 3) - GPUDIFF_INLINE_MAX + 3u) & ~3u)
                                                                           : 0u;
+}
+
+// packed bytes of a leaf's value in an image region (a string's length padded to 4, a number's 8 bytes, nothing for a
+// tag-only leaf); must equal gpudiff_meta_packed (include/gpudiff_format.h), restated like sp_meta_arena because K2
+// compiles it (tests/test_packed_rule.py ties the two together over every tag and length)
+GD_SP_HD inline uint32_t sp_pk(uint32_t m) {
+    const uint32_t tag = m & 7u;
+    return tag == GPUDIFF_TAG_STR ? (((m >> 3) + 3u) & ~3u) : (tag == GPUDIFF_TAG_INT || tag == GPUDIFF_TAG_FLOAT) ? 8u : 0u;
 }
 
 enum SpClass : uint32_t { SP_VAL = 0, SP_KEY = 1, SP_META = 2, SP_ARENA = 3 };
@@ -126,6 +136,46 @@ GD_SP_HD inline uint32_t sp_region_rule(const uint8_t* seg_a, const uint8_t* seg
             const uint32_t leaf = w.cls == SP_ARENA ? sp_arena_owner(ma, L, w.idx) : w.idx;
             if (leaf >= L) return kSpRefuse;
             uint32_t at = 0;  // sorted insert, once
+            while (at < ns && leaves[at] < leaf) at++;
+            if (at < ns && leaves[at] == leaf) continue;
+            if (ns == kSpMaxLeaves) return kSpRefuse;
+            for (uint32_t k = ns; k > at; k--) leaves[k] = leaves[k - 1];
+            leaves[at] = leaf;
+            ns++;
+        }
+    for (uint32_t k = 0; k < ns; k++)
+        if (sp_meta_arena(ma[leaves[k]]) != sp_meta_arena(mb[leaves[k]])) return kSpRefuse;
+    return ns;
+}
+
+// ---- A packed region of the compare image (gpudiff_format.h: gpudiff_meta_packed) is not mapped back to its segment:
+// it holds value bytes alone, leaf i at [P_i, P_{i+1}) with P the exclusive prefix of sp_pk over side A's metas (the
+// pool's: the image has none), so the differing dword at packed byte p is leaf i's, and a byte at or past P_L is the
+// region's final padding.  No key dword, no meta dword and no shifted tail can occur: both sides were packed by A's
+// metas.  The region's changed paths are the keys of the set S of owners when the log did not overflow and |S| <=
+// kSpMaxLeaves; the padded tail lengths of S are compared as above (they are equal unless a meta was changed behind the
+// encoder's back, which the join then sees as before).
+// the leaf that owns packed byte p; L when none does
+GD_SP_HD inline uint32_t sp_packed_owner(const uint32_t* metas, uint32_t L, uint32_t p) {
+    uint32_t off = 0;
+    for (uint32_t i = 0; i < L; i++) {
+        const uint32_t n = sp_pk(metas[i]);
+        if (p - off < n) return i;  // off <= p here
+        off += n;
+    }
+    return L;
+}
+// The rule, one packed region, serially: entries[n] its mismatching chunks (chunk indices in the packed region), ma / mb
+// the two sides' metas[L] in the pool.  Returns |S| with the leaves ascending in leaves[], or kSpRefuse.
+GD_SP_HD inline uint32_t sp_packed_rule(const uint32_t* ma, const uint32_t* mb, uint32_t L, const uint32_t* entries,
+                                        uint32_t n, uint32_t leaves[kSpMaxLeaves]) {
+    uint32_t ns = 0;
+    for (uint32_t q = 0; q < n; q++)
+        for (uint32_t d = 0; d < 4; d++) {
+            if (!((sp_entry_dwords(entries[q]) >> d) & 1u)) continue;
+            const uint32_t leaf = sp_packed_owner(ma, L, (uint32_t)sp_entry_byte(entries[q], d));
+            if (leaf >= L) return kSpRefuse;
+            uint32_t at = 0;
             while (at < ns && leaves[at] < leaf) at++;
             if (at < ns && leaves[at] == leaf) continue;
             if (ns == kSpMaxLeaves) return kSpRefuse;

@@ -402,6 +402,8 @@ SIGNATURES = [
     ("gpudiff_rows_stream_bytes", C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]),
     ("gpudiff_rows_read_bytes", C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]),
     ("gpudiff_rows_image_read_bytes", C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]),
+    ("gpudiff_rows_image_streamed_bytes", C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_uint64)]),
+    ("gpudiff_dbatch_image_streamed_bytes", C.c_int, [_P, _P, C.POINTER(C.c_uint64)]),
     ("gpudiff_dbatch_set_image_capacity", C.c_int, [_P, C.c_uint64]),
     ("gpudiff_dbatch_image_stats", C.c_int, [_P, C.POINTER(ImageStats)]),
     ("gpudiff_diff", C.c_int, [_P, _P, C.POINTER(C.c_uint64)]),
@@ -606,6 +608,17 @@ def image_read_bytes(rows: np.ndarray) -> int:
     return int(out.value)
 
 
+def image_streamed_bytes(rows: np.ndarray, pool: np.ndarray) -> int:
+    """What K2 streams for the imaged pairs among these rows, their parts packed to the values' true lengths by A's
+    metas in pool (gpudiff_rows_image_streamed_bytes); pool: the host batch's, as HostBatch.pool_view gives it."""
+    rows = np.ascontiguousarray(rows, dtype=ROW_DTYPE)
+    pool = np.ascontiguousarray(pool, dtype=np.uint8)
+    out = C.c_uint64()
+    _chk(_lib.gpudiff_rows_image_streamed_bytes(rows.ctypes.data, rows.size, pool.ctypes.data, C.byref(out)),
+         "gpudiff_rows_image_streamed_bytes")
+    return int(out.value)
+
+
 def shard_lpt(weights, world: int) -> np.ndarray:
     """Owner rank per cluster: greedy LPT by weight (gpudiff_shard_lpt; shard.lpt_assign restates it)."""
     w = np.ascontiguousarray(weights, dtype=np.uint64)
@@ -794,6 +807,13 @@ class DeviceBatch:
         """The compare image's capacity in bytes, before the first append; 0: no image
         (gpudiff_dbatch_set_image_capacity).  Default: the pool's capacity."""
         _chk(_lib.gpudiff_dbatch_set_image_capacity(self.h, nbytes), "gpudiff_dbatch_set_image_capacity")
+
+    def image_streamed_bytes(self) -> int:
+        """What K2 streams for the batch's imaged pairs in one pass, summed on the device by the appends
+        (gpudiff_dbatch_image_streamed_bytes); waits for the last append's builder kernel."""
+        out = C.c_uint64()
+        _chk(_lib.gpudiff_dbatch_image_streamed_bytes(self.engine.ctx, self.h, C.byref(out)), "gpudiff_dbatch_image_streamed_bytes")
+        return int(out.value)
 
     def image_stats(self) -> ImageStats:
         st = ImageStats()

@@ -49,7 +49,8 @@ def main():
 
     # what K2 reads from the descriptors, key and shape holes out; the key holes alone out (DESIGN.md §6n's measure); the
     # same with every hole streamed
-    sb = [0, 0, 0, 0]  # ... and [3]: what it reads with the compare image (a tree whose binding has it)
+    sb = [0, 0, 0, 0, 0]  # ... [3]: what it reads with the compare image, by the slots' sizes; [4]: what it streams of
+    # the imaged pairs, their parts packed (a tree whose binding has them)
 
     def cpu(hb):
         if hasattr(G, "stream_bytes"):  # (a parent tree's binding may not have it)
@@ -58,6 +59,8 @@ def main():
             sb[2] += G.stream_bytes(rows)
             if hasattr(G, "image_read_bytes"):
                 sb[3] += G.image_read_bytes(rows)
+            if hasattr(G, "image_streamed_bytes"):
+                sb[4] += G.image_streamed_bytes(rows, hb.pool_view())
             rows = rows.copy()
             rows["flags_b"] &= ~np.uint32(G.OBJ_SPEC_KEYS_EQ)
             sb[1] += G.stream_bytes(rows)
@@ -88,6 +91,8 @@ def main():
         st = db.image_stats()
         out.update(image_read_bytes=sb[3], image_saved_bytes=sb[0] - sb[3], image_bytes_used=int(st.bytes_used),
                    image_capacity=int(st.capacity), image_pairs=int(st.pairs))
+    if sb[4]:  # the host's sum over the appended batches beside the sum the builder kernel kept on the device
+        out.update(image_streamed_bytes_host=sb[4], image_streamed_bytes_device=db.image_streamed_bytes())
     if parts:
         c_flags = np.concatenate([q[0] for q in parts])
         c_offs, base = [np.zeros(1, np.int64)], 0

@@ -2,7 +2,9 @@
 shape holes leave out (gpudiff_pair_stream_bytes, include/gpudiff_format.h), summed on the host from the product
 encoder's rows: both sums, with the key holes alone (gpudiff_rows_stream_bytes, DESIGN.md §6n's measure) and with the
 shape holes the kernel honours (gpudiff_rows_read_bytes), and what it reads when every pair that can be is streamed from
-the batch's compare image (gpudiff_rows_image_read_bytes), with and without the status shape bit.  No GPU needed.
+the batch's compare image (gpudiff_rows_image_read_bytes, the slots' sum), with and without the status shape bit, and
+with the imaged pairs' parts packed to their values' true lengths (gpudiff_rows_image_streamed_bytes: what K2 really
+streams).  No GPU needed.
 
     python tools/keys_hole_bytes.py --config config3 --population 200000 --pairs 100000
 """
@@ -31,7 +33,8 @@ def main():
     n = min(args.pairs, pop.n)
     out = dict(config=args.config, pairs=n, format_bytes=0, stream_bytes=0, read_bytes=0, stream_bytes_no_holes=0,
                sizes_eq=0, keys_eq=0, shape_eq=0, pairs_with_hole=0, pairs_with_shape_hole=0, image_read_bytes=0,
-               image_read_bytes_spec_only=0, imaged=0, imaged_stat_sized=0, imaged_stat_shape_eq=0)
+               image_read_bytes_spec_only=0, imaged=0, imaged_stat_sized=0, imaged_stat_shape_eq=0,
+               image_slot_bytes_imaged=0, image_streamed_bytes=0)
     pos = 0
     while pos < n:
         m = min(65536, n - pos)
@@ -60,6 +63,10 @@ def main():
         nostat = rows.copy()
         nostat["flags_b"] &= ~np.uint32(G.OBJ_STAT_SHAPE_EQ)
         out["image_read_bytes_spec_only"] += G.image_read_bytes(nostat)
+        # ... and its parts are packed to the values' true lengths: what K2 streams of the imaged pairs, beside what
+        # their slots would give (image_read_bytes is the slots' sum, an upper bound)
+        out["image_slot_bytes_imaged"] += G.image_read_bytes(rows[eq & sbit])
+        out["image_streamed_bytes"] += G.image_streamed_bytes(rows, hb.pool_view())
         stat_sz = ((rows["flags_b"] & G.OBJ_HAS_STATUS) != 0) & (rows["stat_l_a"] == rows["stat_l_b"]) & (
             rows["stat_ar_a"] == rows["stat_ar_b"])
         out["imaged"] += int((eq & sbit).sum())
@@ -80,6 +87,10 @@ def main():
     out["image_saved_share"] = (out["read_bytes"] - out["image_read_bytes"]) / out["read_bytes"]
     out["image_saved_bytes_per_pair_spec_only"] = (out["read_bytes"] - out["image_read_bytes_spec_only"]) / n
     out["image_saved_share_spec_only"] = (out["read_bytes"] - out["image_read_bytes_spec_only"]) / out["read_bytes"]
+    out["packed_read_bytes"] = out["image_read_bytes"] - out["image_slot_bytes_imaged"] + out["image_streamed_bytes"]
+    out["packed_read_bytes_per_pair"] = out["packed_read_bytes"] / n
+    out["packed_saved_bytes_per_pair"] = (out["image_read_bytes"] - out["packed_read_bytes"]) / n
+    out["packed_saved_share"] = (out["image_read_bytes"] - out["packed_read_bytes"]) / out["image_read_bytes"]
     print(json.dumps(out))
     eng.close()
     pop.close()
